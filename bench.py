@@ -13,10 +13,13 @@ N > 1 (one process per GPU, torchrun): the window is sharded by grid-cell column
 rank holds 10M points of its band (weak scaling), per-rank top-k records are all-gathered over
 RCCL and merged on every rank.
 
-Prints ONE JSON line (rank 0) with the metric, a roofline object for the dominant kernel
-(knn_scan, HIP events on its stream over the timed region) and the CPU baselines (the oracle's
-reference-shaped evaluator on every thread of the CPU share and on one, plus an optimised OpenMP
-scan; see cpu_baselines).
+Prints ONE JSON line (rank 0) with the metric and a roofline object for the dominant kernel
+(knn_scan, HIP events on its stream over the timed region).  A plain run sets up, warms up, times
+`--steps` windows, writes the last timed window's record if `--dump-outputs DIR` is given, and
+prints the line.  `--full` adds what takes runs of its own: the oracle verification of every
+window, the CPU baselines (the oracle's reference-shaped evaluator on every thread of the CPU
+share and on one, plus an optimised OpenMP scan; see cpu_baselines), the per-kernel breakdown and
+the host-buffer boundary; without it those keys of the line are null.
 """
 from __future__ import annotations
 
@@ -186,6 +189,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="knn: also verify every window against the oracle, run the CPU baselines, the per-kernel "
+                         "breakdown and the host-buffer boundary (each takes runs of its own; off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="knn: after the timed steps, write the record of the last timed window (what the caller "
+                         "of the timed path receives) as DIR/knn_<field>.npy, float64")
     ap.add_argument("--points", type=int, default=None, help="points per window per GPU (kNN default 10M)")
     ap.add_argument("--workload", default="knn", choices=("knn", "range", "ppoly", "join", "pjoin", "sliding", "csv", "geojson", "polyknn", "bucket"),
                     help="knn = the headline line (BASELINE configs[1]); range/ppoly/join/pjoin/sliding/csv/polyknn/"
@@ -203,7 +212,7 @@ def main():
     ap.add_argument("--radius", type=float, default=0.5)
     ap.add_argument("--grid", type=int, default=500)
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
-                    help="CPU baseline budget, split over its three lines (rank 0, N=1)")
+                    help="--full: CPU baseline budget, split over its three lines (rank 0, N=1)")
     ap.add_argument("--cpu-sample", type=int, default=1_000_000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--join-stream", action="store_true",
@@ -250,6 +259,8 @@ def main():
 
     W.CLUSTERED = args.clustered
     if args.workload != "knn":
+        if args.dump_outputs:
+            ap.error("--dump-outputs is implemented for the knn workload only")
         W.run(args)
         return
     if args.points is None:
@@ -444,10 +455,21 @@ def main():
             per_window[j] = (o, d, ix)
     assert fallbacks == 0, f"{fallbacks} windows needed the exact fallback inside the timed region"
 
-    # per-kernel breakdown (separate, untimed pass), steady state and cold (no hint: sample each window)
+    if args.dump_outputs and rank == 0:
+        # the record of the last timed window, as its caller receives it (N > 1: the merged record);
+        # the windows' seeds are fixed, so the same arguments give the same inputs in every run
+        last = total_steps - 1
+        st, o, d, ix = hstr.decode(last) if hstr is not None else host.decode(last)
+        if hstr is None and sdict is not None:
+            o = np.array([int(s_[3:]) for s_ in sdict.decode_bytes(o)], np.int64)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("status", np.array([st])), ("objID", o), ("dist", d), ("index", ix)):
+            np.save(os.path.join(args.dump_outputs, f"knn_{name}.npy"), np.asarray(a, np.float64))
+
+    # --full: per-kernel breakdown (separate, untimed pass), steady state and cold (no hint: sample each window)
     kid_all = (1 << _lib.K_KNN_SCAN) | (1 << _lib.K_KNN_SAMPLE) | (1 << _lib.K_KNN_SELECT)
-    breakdown = {}
-    for tag, hint in (("", 1), ("cold_", 0)):
+    breakdown = {} if args.full else None
+    for tag, hint in ((("", 1), ("cold_", 0)) if args.full else ()):
         _lib.check(_lib.lib().gf_knn_plan_set_hint(plan, hint), ctx.handle, "hint")
         # both streams busy before the first timed event (an event recorded on an idle stream
         # can carry the timestamp of that stream's last, long-finished command)
@@ -475,7 +497,7 @@ def main():
     # pageable), then the host-resident pipeline: NH distinct pinned host windows streamed
     # through two gf_windows -- upload(i+1) on the window's copy stream overlaps evaluate(i)
     pcie = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         bpp = 24
         NH = 3
         pins, hws = [], []
@@ -572,7 +594,7 @@ def main():
 
     verified = None
     cpu = None
-    if rank == 0 and world > 1 and not args.no_verify and world * n <= 100_000_000:
+    if args.full and rank == 0 and world > 1 and not args.no_verify and world * n <= 100_000_000:
         # the merged record of window 0 (every rank's band of it, all-gathered over the
         # backend and merged on the device) == the oracle on the whole window: rank 0
         # regenerates the other ranks' bands (same seeds) and concatenates them in rank order,
@@ -596,7 +618,7 @@ def main():
         log(f"oracle verification of window 0 over {world} ranks x {n} points: {verified} "
             f"({time.perf_counter()-t:.1f}s)")
         assert verified, "merged multi-rank kNN differs from the oracle"
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle as O
 

@@ -42,7 +42,8 @@ def _run_two_ranks(extra, launcher=False):
     if launcher:
         pre += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                 "--master-addr", "127.0.0.1", "--master-port", str(_free_port())]
-    cmd = pre + [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--no-cpu-baseline"] + extra
+    cmd = pre + [os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--dist-backend", "gloo",
+                 "--no-cpu-baseline"] + extra
     env = dict(os.environ, OMP_NUM_THREADS="4")
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=400)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-6000:]
