@@ -60,7 +60,10 @@ extern "C" {
 #define GF_K_CSV_PARSE   9  /* CSV ingest: the per-line parse kernel */
 #define GF_K_BUCKET      10 /* K2 bucketing by cell (gf_bucket_by_cell) */
 #define GF_K_JOIN_COMPACT 11 /* join: packing of the probe's task regions */
-#define GF_K_COUNT       12
+#define GF_K_TRAJ_GROUP  12 /* trajectories: the group-by-objID kernels (its radix passes count as GF_K_BUCKET) */
+#define GF_K_TSTATS      13 /* trajectories: tStats */
+#define GF_K_TRAJ_SELECT 14 /* trajectories: sub-trajectory extraction */
+#define GF_K_COUNT       15
 
 typedef struct gf_ctx gf_ctx;
 
@@ -93,7 +96,7 @@ typedef struct {
   const double* x;
   const double* y;
   const int64_t* objID;  /* objID keys (above); needed by kNN only */
-  const int64_t* ts;     /* timeStampMillisec; unused by window evaluation */
+  const int64_t* ts;     /* timeStampMillisec; read by the trajectory operators only */
   int64_t n;
 } gf_points;
 
@@ -616,6 +619,54 @@ int gf_join_ppoly_run(gf_range_plan* plan, const gf_grid* ugrid, const gf_points
 int gf_join_ppoly(gf_ctx* ctx, const gf_grid* ugrid, const gf_grid* qgrid, const gf_points* points,
                   const gf_polygons* polys, double r, int approximate, int metric, uint32_t* pairs,
                   int64_t cap, int64_t* npairs);
+
+/* ---- trajectories -----------------------------------------------------------------------
+ * The reference's t* operators (TStatsQuery, PointPolygonTRangeQuery, PointPointTKNNQuery, ...)
+ * treat a window as a set of TRAJECTORIES: the points of one objID in arrival order
+ * (keyBy(objID), then `for (Point p : input)`, TStatsQuery.java:148-189).  gf_traj_group is that
+ * group-by for a device-resident window (needs pts->objID; n < 2^32):
+ *   keys[ntraj]        the distinct objID keys in FIRST-OCCURRENCE order: trajectory t is the objID
+ *                      whose first point has the t-th smallest index (Flink's keyBy emission order
+ *                      is unspecified; this one never depends on scheduling);
+ *   seg_off[ntraj + 1] segment offsets into perm;
+ *   perm[n]            window indices, ascending inside each segment (arrival order).
+ * Any int64 is a legal key (numeric, dictionary, GF_OBJID_NULL: a null objID is a group like any
+ * other).  The result is identical from run to run.  Sync.  *out == NULL: a new groups object;
+ * otherwise that object (of the same context) is regrouped and its device workspace reused. */
+typedef struct gf_traj_groups gf_traj_groups;
+int  gf_traj_group(gf_ctx* ctx, const gf_points* pts, gf_traj_groups** out);
+void gf_traj_groups_destroy(gf_traj_groups* g);
+int  gf_traj_groups_info(const gf_traj_groups* g, int64_t* ntraj, int64_t* n);
+/* Sync: host copies of keys[ntraj], seg_off[ntraj + 1], perm[n]; any may be NULL. */
+int  gf_traj_groups_read(gf_traj_groups* g, int64_t* keys, int64_t* seg_off, uint32_t* perm);
+/* Testing / tuning: trajectories of at least `len` points take tStats' block-per-trajectory path
+ * (len >= 1; 0 = the default, 2048).  Results are identical for any value. */
+int  gf_traj_groups_set_long_threshold(gf_traj_groups* g, int64_t len);
+/* TStatsQuery.TStatsQueryWFunction.apply (TStatsQuery.java:154-188) per trajectory, over its points
+ * in arrival order (pts: the grouped window; needs x, y, ts):
+ *   last = 0; for p: if (last == 0) { last = p.ts; X, Y = p; S = 0.0; T = 0 }
+ *                    else if (p.ts > last) { S += sqrt(dy*dy + dx*dx); T += p.ts - last; last = p.ts; X, Y = p }
+ *   row = (key, S, T, S / (double)T)        (DistanceFunctions.java:60-63; fewer than two counted
+ *                                            points: 0.0, 0, NaN)
+ * S is the sequential left-to-right binary64 sum, bit for bit.  Timestamps must be >= 0 (epoch
+ * milliseconds): points with ts == 0 never count and a point counts iff its ts exceeds every
+ * earlier ts of its trajectory; negative timestamps are outside the contract.
+ * id_set (host, nset keys; PointTStatsQuery.java:76-84 trajIDSet): non-empty = only trajectories
+ * whose key is in it.  Rows in first-occurrence order into HOST arrays (any may be NULL): *count =
+ * all rows, at most cap written (as gf_bitmap_to_indices).  Sync. */
+int  gf_tstats_run(gf_traj_groups* g, const gf_points* pts, const int64_t* id_set, int64_t nset,
+                   int64_t* keys, double* spatial, int64_t* temporal, double* speed, int64_t cap, int64_t* count);
+/* Sub-trajectories: every trajectory with at least one point flagged in `bitmap` (device
+ * uint64[(n+63)/64], e.g. gf_range_run's), in full, as CSR in HOST arrays -- the assembly half of the
+ * window-based tRange / tKnn / tJoin (PointPolygonTRangeQuery.java:158-176, PointPointTKNNQuery.java:
+ * 241-270; single-point trajectories are emitted too, the caller applies the reference's size rules).
+ * Trajectories in first-occurrence order: keys[m], off[m + 1]; trajectory j owns points
+ * [off[j], off[j+1]) of x, y, ts, idx (idx = window index), in arrival order.  *ntraj_out = m and
+ * *npts_out = all their points; at most cap_traj trajectories (keys, and off[0 .. min(m, cap_traj)])
+ * and cap_pts points are written.  Any output array may be NULL.  Sync. */
+int  gf_traj_select(gf_traj_groups* g, const gf_points* pts, const uint64_t* bitmap, int64_t* keys, int64_t* off,
+                    int64_t cap_traj, double* x, double* y, int64_t* ts, uint32_t* idx, int64_t cap_pts,
+                    int64_t* ntraj_out, int64_t* npts_out);
 
 /* ---- pinned host memory ---------------------------------------------------------------
  * Mapped, portable host memory: kernels write kNN records straight into it (pass it as the

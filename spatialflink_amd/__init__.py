@@ -4,13 +4,14 @@ The Java operators' per-window bodies (range, kNN, join) run as hand-written HIP
 for gfx950 behind the C ABI in include/geoflink_hip.h; this package is the host-side
 mirror of the reference operator API (UniformGrid, Point, Polygon, QueryConfiguration,
 PointPointRangeQuery, PointPolygonRangeQuery, PointPointKNNQuery, PointPointJoinQuery,
-PointPolygonKNNQuery, PointPolygonJoinQuery).
+PointPolygonKNNQuery, PointPolygonJoinQuery, PointTStatsQuery).
 """
 from . import _lib, sharding
 from .spatialIndices import UniformGrid, generateCellIDStr, getIntCellIndices, padLeadingZeroesToInt
 from .spatialObjects import ObjIdDict, Point, PointWindow, Polygon, PolygonSet
 from .spatialOperators import (KNNResult, PinnedRecords, PointPointJoinQuery, PointPointKNNQuery, PointPointRangeQuery,
-                               PointPolygonJoinQuery, PointPolygonKNNQuery,
+                               PointPolygonJoinQuery, PointPolygonKNNQuery, PointTStatsQuery, SubTrajectories,
+                               TrajectoryGroups, TStatsResult, group_by_objid, sub_trajectories,
                                PointPolygonRangeQuery, QueryConfiguration, QueryType, RangeResult, assign_cells,
                                bucket_by_cell, knn_merge_host, synthetic_uniform,
                                synthetic_clustered)
@@ -18,6 +19,7 @@ from .spatialStreams import Deserialization
 from .windows import SlidingKNNQuery, SlidingRangeQuery, SlidingWindows
 
 __all__ = [
+    "PointTStatsQuery", "TStatsResult", "SubTrajectories", "TrajectoryGroups", "group_by_objid", "sub_trajectories",
     "SlidingWindows", "SlidingKNNQuery", "SlidingRangeQuery", "Deserialization", "PointPolygonKNNQuery", "PointPolygonJoinQuery",
     "UniformGrid", "ObjIdDict", "Point", "Polygon", "PolygonSet", "PointWindow", "QueryType", "QueryConfiguration",
     "PointPointRangeQuery", "PointPolygonRangeQuery", "PointPointKNNQuery", "PointPointJoinQuery", "RangeResult",

@@ -38,7 +38,7 @@ FLAG_GEOJSON_WAVE = 16
 FLAG_GEOJSON_CHECK = 32
 FLAG_JOIN_STREAM = 8
 (K_KNN_SCAN, K_KNN_SAMPLE, K_KNN_SELECT, K_RANGE_SCAN, K_ASSIGN, K_JOIN_PROBE, K_RANGE_TEST, K_JOIN_BUCKET,
- K_KNN_MERGE, K_CSV_PARSE, K_BUCKET, K_JOIN_COMPACT) = range(12)
+ K_KNN_MERGE, K_CSV_PARSE, K_BUCKET, K_JOIN_COMPACT, K_TRAJ_GROUP, K_TSTATS, K_TRAJ_SELECT) = range(15)
 
 # Every symbol include/geoflink_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = [
@@ -65,6 +65,8 @@ EXPORTS = [
     "gf_host_pinned", "gf_comm_available", "gf_comm_unique_id", "gf_comm_create", "gf_comm_create_all",
     "gf_comm_destroy", "gf_comm_info", "gf_comm_last_error", "gf_comm_check", "gf_knn_exchange_batch",
     "gf_knn_exchange_strings_batch", "gf_knn_exchange_group",
+    "gf_traj_group", "gf_traj_groups_destroy", "gf_traj_groups_info", "gf_traj_groups_read",
+    "gf_traj_groups_set_long_threshold", "gf_tstats_run", "gf_traj_select",
 ]
 
 
@@ -234,6 +236,13 @@ def lib():
             "gf_knn_exchange_batch": ([P, P, i32, P, i32, P], C.c_int),
             "gf_knn_exchange_strings_batch": ([P, P, i32, i64, P, i32, P], C.c_int),
             "gf_knn_exchange_group": ([i32, P, P, i32, P, i32, P], C.c_int),
+            "gf_traj_group": ([P, C.POINTER(GfPoints), C.POINTER(P)], C.c_int),
+            "gf_traj_groups_destroy": ([P], None),
+            "gf_traj_groups_info": ([P, pi64, pi64], C.c_int),
+            "gf_traj_groups_read": ([P, P, P, P], C.c_int),
+            "gf_traj_groups_set_long_threshold": ([P, i64], C.c_int),
+            "gf_tstats_run": ([P, C.POINTER(GfPoints), P, i64, P, P, P, P, i64, pi64], C.c_int),
+            "gf_traj_select": ([P, C.POINTER(GfPoints), P, P, P, i64, P, P, P, P, i64, pi64, pi64], C.c_int),
         }
         for name, (argt, rest) in sig.items():
             if os.environ.get("GF_LIB_PATH") and not hasattr(L, name):

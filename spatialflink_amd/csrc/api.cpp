@@ -227,6 +227,8 @@ const char* build_tag_k_range_hip();
 const char* build_tag_k_join_hip();
 const char* build_tag_k_csv_hip();
 const char* build_tag_k_objid_hip();
+const char* build_tag_traj_cpp();
+const char* build_tag_k_traj_hip();
 struct UnitTag {
   const char* unit;
   const char* (*tag)();
@@ -237,7 +239,8 @@ static const UnitTag kUnitTags[] = {
     {"objid.cpp", build_tag_objid_cpp},     {"k_points.hip", build_tag_k_points_hip},
     {"k_knn.hip", build_tag_k_knn_hip},     {"k_range.hip", build_tag_k_range_hip},
     {"k_join.hip", build_tag_k_join_hip},   {"k_csv.hip", build_tag_k_csv_hip},
-    {"k_objid.hip", build_tag_k_objid_hip},
+    {"k_objid.hip", build_tag_k_objid_hip}, {"traj.cpp", build_tag_traj_cpp},
+    {"k_traj.hip", build_tag_k_traj_hip},
 };
 // run-time A/B knobs (valid alternative paths, never wrong results): reported, not refused
 static const char* const kEnvKnobs[] = {"GF_K2_LSD", "GF_K2_SELFCOUNT", "GF_K2_ROWSORT", "GF_K2_MERGE", "GF_JOIN_BAND_PER_CU", "GF_JOIN_ROWPROBE",

@@ -531,6 +531,72 @@ hipError_t launch_csv_parse(gf_ctx* ctx, const CsvArgs& a);
 hipError_t launch_pane_bounds(hipStream_t s, const int64_t* ts, int64_t n, int64_t pane_ms, int64_t first_pane,
                               int32_t nb, int64_t* bounds);
 
+// trajectory operators (k_traj.hip, traj.cpp)
+constexpr unsigned long long kTrajEmpty = 0x7FFFFFFFFFFFFFFEull;  // the table's empty marker (a legal key: its own slot)
+constexpr int64_t kTrajLongLen = 2048;  // default: trajectories of at least this many points take tStats' block path
+struct TrajTable {
+  unsigned long long* key;  // [mask + 2]: the table, then the slot of the points whose key is kTrajEmpty
+  uint32_t* first;          // [mask + 2] smallest point index of the slot; after traj_assign its dense id
+  uint64_t mask;            // slots - 1 (a power of two >= 2n)
+};
+struct TrajGroupArgs {
+  TrajTable t;
+  const int64_t* objID;
+  int64_t n;
+  uint32_t* flag;           // [n] first points
+  const uint32_t* rank;     // [n + 1] their exclusive scan
+  int64_t* keys;            // [ntraj]
+  uint32_t* did;            // [n] dense id per point
+  const uint32_t* sorted;   // [n] dense id per perm position
+  uint32_t ntraj;
+  uint32_t* seg_off;        // [ntraj + 1]
+};
+// stage 0: clear + insert + flag; 1: assign + ids; 2: seg_off from the sorted ids
+hipError_t launch_traj_group(gf_ctx* ctx, int stage, const TrajGroupArgs& a);
+struct TStatsArgs {
+  const double* x;
+  const double* y;
+  const int64_t* ts;
+  const uint32_t* perm;
+  const uint32_t* seg_off;
+  int64_t ntraj;
+  uint32_t long_len;        // segments of at least this many points go to the block path
+  double* S;                // [ntraj] spatial length
+  int64_t* T;               // [ntraj] temporal length
+  double* V;                // [ntraj] S / (double)T
+  uint32_t* long_list;      // [ntraj]
+  uint32_t* long_count;     // zero before the launch
+};
+hipError_t launch_tstats(gf_ctx* ctx, const TStatsArgs& a);
+// stage 0: sel[t] = keys[t] in set (sorted, distinct); 1: the selected rows packed at rank[t]
+hipError_t launch_tstats_filter(gf_ctx* ctx, const TStatsArgs& a, const int64_t* keys, const int64_t* set, int64_t nset,
+                                uint32_t* sel, const uint32_t* rank, int64_t* ok, double* oS, int64_t* oT, double* oV,
+                                int stage);
+struct TrajSelectArgs {
+  const double* x;
+  const double* y;
+  const int64_t* ts;
+  int64_t n, ntraj;
+  const uint64_t* bitmap;
+  const uint32_t* did;
+  const uint32_t* sorted;
+  const uint32_t* perm;
+  const uint32_t* seg_off;
+  const int64_t* keys;
+  uint32_t* hit;            // [ntraj + 1] zero before stage 0 (entry ntraj stays 0)
+  uint32_t* len;            // [ntraj + 1]
+  const uint32_t* row;      // [ntraj + 1] scan of hit
+  const uint32_t* off;      // [ntraj + 1] scan of len
+  int64_t* okeys;           // [ntraj]
+  uint32_t* ooff;           // [ntraj + 1]
+  double* ox;               // [n]
+  double* oy;
+  int64_t* ots;
+  uint32_t* oidx;
+};
+// stage 0: hit + lens; 1: gather
+hipError_t launch_traj_select(gf_ctx* ctx, int stage, const TrajSelectArgs& a);
+
 hipError_t launch_knn_sample(gf_ctx* ctx, const KnnSampleArgs& a);
 hipError_t launch_knn_scan(gf_ctx* ctx, const KnnScanArgs& a, int blocks, int unroll, int nt);
 hipError_t launch_knn_select(gf_ctx* ctx, const KnnSelectArgs& a);

@@ -1,0 +1,338 @@
+// traj.cpp -- trajectory entry points of the C ABI: gf_traj_group (a window grouped by objID),
+// gf_tstats_run (TStatsQuery.java:154-188 per trajectory), gf_traj_select (sub-trajectories of a
+// hit bitmap).  The kernels are in k_traj.hip; the stable sort by dense trajectory id reuses the
+// LSD radix passes of k_points.hip.  The groups object owns its device workspace (grow-only) and is
+// reused across windows.
+#define GF_TU_NAME traj_cpp
+#include "gf_buildtag.hpp"  // first: records this unit's command-line defines
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "gf_internal.hpp"
+
+using namespace gf;
+
+namespace {
+// a grow-only device buffer
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  int reserve(gf_ctx* ctx, size_t need) {
+    if (need <= bytes) return GF_OK;
+    GF_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // queued work may still read the old one
+    if (p) hipFree(p);
+    p = nullptr;
+    bytes = 0;
+    GF_HIP_CHECK(ctx, hipMalloc(&p, need));
+    bytes = need;
+    return GF_OK;
+  }
+  void release() {
+    if (p) hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  template <class T>
+  T* as() const { return (T*)p; }
+};
+}  // namespace
+
+struct gf_traj_groups {
+  gf_ctx* ctx = nullptr;
+  int64_t n = 0, ntraj = 0;
+  int64_t long_len = kTrajLongLen;
+  // grouping
+  DevBuf tkey, tfirst;       // the hash table (+ the empty marker's slot)
+  DevBuf kbuf[2], vbuf[2];   // radix ping-pong (n + 1 each); kbuf[1] = first-point flags, vbuf[1] = their scan
+  DevBuf did, perm, keys, seg_off, mat, mats, scan_tmp;
+  int sorted_in = 0;         // kbuf[sorted_in] = dense id per perm position
+  // tStats
+  DevBuf S, T, V, long_list, counters, set, sel, srank, ck, cS, cT, cV;
+  // sub-trajectories
+  DevBuf hit, len, row, off, okeys, ooff, ox, oy, ots, oidx;
+  DevBuf* all[36] = {&tkey, &tfirst, &kbuf[0], &kbuf[1], &vbuf[0], &vbuf[1], &did, &perm, &keys, &seg_off, &mat, &mats,
+                     &scan_tmp, &S, &T, &V, &long_list, &counters, &set, &sel, &srank, &ck, &cS, &cT, &cV, &hit, &len,
+                     &row, &off, &okeys, &ooff, &ox, &oy, &ots, &oidx, nullptr};
+};
+
+static int scan_u32(gf_traj_groups* G, const uint32_t* in, int64_t L, uint32_t* out) {
+  gf_ctx* ctx = G->ctx;
+  if (int st = G->scan_tmp.reserve(ctx, scan_tmp_elems(L) * sizeof(uint32_t))) return st;
+  GF_HIP_CHECK(ctx, launch_exclusive_scan(ctx->stream, in, L, out, G->scan_tmp.as<uint32_t>()));
+  return GF_OK;
+}
+
+template <class T>
+static int read_back(gf_ctx* ctx, T* host, const void* dev, size_t count) {
+  if (!host || count == 0) return GF_OK;
+  GF_HIP_CHECK(ctx, hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+  return GF_OK;
+}
+
+extern "C" int gf_traj_group(gf_ctx* ctx, const gf_points* pts, gf_traj_groups** out) {
+  if (!ctx || !out || !pts) return set_err(ctx, GF_ERR_ARG, "gf_traj_group: null argument");
+  if (pts->n < 0 || pts->n > (int64_t)UINT32_MAX) return set_err(ctx, GF_ERR_ARG, "gf_traj_group: need 0 <= n < 2^32");
+  if (pts->n > 0 && !pts->objID) return set_err(ctx, GF_ERR_ARG, "gf_traj_group: null objID");
+  if (*out && (*out)->ctx != ctx) return set_err(ctx, GF_ERR_ARG, "gf_traj_group: groups of another context");
+  int st = bind(ctx);
+  if (st) return st;
+  const bool fresh = *out == nullptr;
+  gf_traj_groups* G = fresh ? new gf_traj_groups() : *out;
+  G->ctx = ctx;
+  auto fail = [&](int code) {
+    if (fresh) gf_traj_groups_destroy(G);
+    else G->n = G->ntraj = 0;
+    return code;
+  };
+  const int64_t n = pts->n;
+  G->n = n;
+  G->ntraj = 0;
+  if ((st = G->seg_off.reserve(ctx, sizeof(uint32_t)))) return fail(st);
+  if (n == 0) {
+    hipError_t e = hipMemsetAsync(G->seg_off.p, 0, sizeof(uint32_t), ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(hip_err(ctx, e, "gf_traj_group"));
+    *out = G;
+    return GF_OK;
+  }
+  uint64_t slots = 64;
+  while (slots < 2 * (uint64_t)n) slots <<= 1;
+  const size_t w = sizeof(uint32_t) * (size_t)(n + 1);
+  if ((st = G->tkey.reserve(ctx, (slots + 1) * sizeof(unsigned long long))) ||
+      (st = G->tfirst.reserve(ctx, (slots + 1) * sizeof(uint32_t))) || (st = G->kbuf[0].reserve(ctx, w)) ||
+      (st = G->kbuf[1].reserve(ctx, w)) || (st = G->vbuf[0].reserve(ctx, w)) || (st = G->vbuf[1].reserve(ctx, w)) ||
+      (st = G->did.reserve(ctx, w)) || (st = G->perm.reserve(ctx, w)))
+    return fail(st);
+  TrajGroupArgs a{};
+  a.t.key = G->tkey.as<unsigned long long>();
+  a.t.first = G->tfirst.as<uint32_t>();
+  a.t.mask = slots - 1;
+  a.objID = pts->objID;
+  a.n = n;
+  a.flag = G->kbuf[1].as<uint32_t>();
+  a.rank = G->vbuf[1].as<uint32_t>();
+  a.did = G->did.as<uint32_t>();
+  hipError_t e = launch_traj_group(ctx, 0, a);
+  if (e != hipSuccess) return fail(hip_err(ctx, e, "traj insert"));
+  if ((st = scan_u32(G, a.flag, n, G->vbuf[1].as<uint32_t>()))) return fail(st);
+  // the trajectory count sizes the outputs and the sort's digits: the call's one mid-way host read
+  uint32_t ntraj = 0;
+  e = hipMemcpyAsync(&ntraj, a.rank + n, sizeof ntraj, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) return fail(hip_err(ctx, e, "traj count"));
+  if (ntraj < 1 || (int64_t)ntraj > n) return fail(set_err(ctx, GF_ERR_HIP, "gf_traj_group: inconsistent trajectory count"));
+  if ((st = G->keys.reserve(ctx, sizeof(int64_t) * (size_t)ntraj)) ||
+      (st = G->seg_off.reserve(ctx, sizeof(uint32_t) * ((size_t)ntraj + 1))))
+    return fail(st);
+  a.keys = G->keys.as<int64_t>();
+  a.ntraj = ntraj;
+  a.seg_off = G->seg_off.as<uint32_t>();
+  if ((e = launch_traj_group(ctx, 1, a)) != hipSuccess) return fail(hip_err(ctx, e, "traj assign"));
+  // stable LSD radix over the dense ids (ids < ntraj): digits of <= kRadixMaxBits bits
+  int bits = 1;
+  while (((uint64_t)1 << bits) < (uint64_t)ntraj) ++bits;
+  const int passes = (bits + kRadixMaxBits - 1) / kRadixMaxBits, pbits = (bits + passes - 1) / passes;
+  const int64_t tiles = (n + radix_tile() - 1) / radix_tile();
+  const int blocks = (int)std::min<int64_t>(std::max<int64_t>(tiles / 4, 1), (int64_t)radix_max_blocks(ctx->num_cus));
+  const int64_t mat = ((int64_t)1 << pbits) * blocks;
+  if ((st = G->mat.reserve(ctx, sizeof(uint32_t) * (size_t)mat)) ||
+      (st = G->mats.reserve(ctx, sizeof(uint32_t) * (size_t)(mat + 1))))
+    return fail(st);
+  RadixArgs r{};
+  r.tile = radix_tile();
+  r.n = n;
+  r.bits = pbits;
+  r.nblk = blocks;
+  r.M = G->mat.as<uint32_t>();
+  r.Ms = G->mats.as<uint32_t>();
+  for (int p = 0; p < passes; ++p) {
+    r.kin = p == 0 ? G->did.as<uint32_t>() : G->kbuf[(p - 1) & 1].as<uint32_t>();
+    r.vin = p == 0 ? nullptr : G->vbuf[(p - 1) & 1].as<uint32_t>();  // pass 0: the index is the position
+    r.kout = G->kbuf[p & 1].as<uint32_t>();
+    r.vout = p == passes - 1 ? G->perm.as<uint32_t>() : G->vbuf[p & 1].as<uint32_t>();
+    r.shift = p * pbits;
+    if ((e = launch_radix(ctx, 0, r, blocks)) != hipSuccess) return fail(hip_err(ctx, e, "traj radix histogram"));
+    if ((st = scan_u32(G, r.M, mat, G->mats.as<uint32_t>()))) return fail(st);
+    if ((e = launch_radix(ctx, 1, r, blocks)) != hipSuccess) return fail(hip_err(ctx, e, "traj radix scatter"));
+  }
+  G->sorted_in = (passes - 1) & 1;
+  a.sorted = G->kbuf[G->sorted_in].as<uint32_t>();
+  if ((e = launch_traj_group(ctx, 2, a)) != hipSuccess) return fail(hip_err(ctx, e, "traj bounds"));
+  if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(hip_err(ctx, e, "gf_traj_group"));
+  G->ntraj = ntraj;
+  *out = G;
+  return GF_OK;
+}
+
+extern "C" void gf_traj_groups_destroy(gf_traj_groups* G) {
+  if (!G) return;
+  if (G->ctx) {
+    hipSetDevice(G->ctx->device);
+    hipStreamSynchronize(G->ctx->stream);
+  }
+  for (DevBuf** b = G->all; *b; ++b) (*b)->release();
+  delete G;
+}
+
+extern "C" int gf_traj_groups_info(const gf_traj_groups* G, int64_t* ntraj, int64_t* n) {
+  if (!G) return GF_ERR_ARG;
+  if (ntraj) *ntraj = G->ntraj;
+  if (n) *n = G->n;
+  return GF_OK;
+}
+
+extern "C" int gf_traj_groups_set_long_threshold(gf_traj_groups* G, int64_t len) {
+  if (!G || len < 0 || len > (int64_t)UINT32_MAX) return GF_ERR_ARG;
+  G->long_len = len == 0 ? kTrajLongLen : len;
+  return GF_OK;
+}
+
+extern "C" int gf_traj_groups_read(gf_traj_groups* G, int64_t* keys, int64_t* seg_off, uint32_t* perm) {
+  if (!G) return GF_ERR_ARG;
+  gf_ctx* ctx = G->ctx;
+  int st = bind(ctx);
+  if (st) return st;
+  std::vector<uint32_t> so;
+  if (seg_off) so.resize((size_t)G->ntraj + 1);
+  if ((st = read_back(ctx, keys, G->keys.p, (size_t)G->ntraj)) ||
+      (st = read_back(ctx, seg_off ? so.data() : nullptr, G->seg_off.p, so.size())) ||
+      (st = read_back(ctx, perm, G->perm.p, (size_t)G->n)))
+    return st;
+  GF_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < so.size(); ++i) seg_off[i] = (int64_t)so[i];
+  return GF_OK;
+}
+
+// the grouped window again, with the columns tStats / the extraction read
+static int check_traj_points(gf_traj_groups* G, const gf_points* pts, const char* who) {
+  gf_ctx* ctx = G->ctx;
+  if (!pts || pts->n != G->n) return set_err(ctx, GF_ERR_ARG, std::string(who) + ": pts is not the grouped window");
+  if (pts->n > 0 && (!pts->x || !pts->y || !pts->ts)) return set_err(ctx, GF_ERR_ARG, std::string(who) + ": null x / y / ts");
+  return GF_OK;
+}
+
+extern "C" int gf_tstats_run(gf_traj_groups* G, const gf_points* pts, const int64_t* id_set, int64_t nset, int64_t* keys,
+                             double* spatial, int64_t* temporal, double* speed, int64_t cap, int64_t* count) {
+  if (!G || !G->ctx) return GF_ERR_ARG;
+  gf_ctx* ctx = G->ctx;
+  if (!count || cap < 0 || nset < 0 || (nset > 0 && !id_set)) return set_err(ctx, GF_ERR_ARG, "gf_tstats_run: bad argument");
+  int st = check_traj_points(G, pts, "gf_tstats_run");
+  if (st) return st;
+  *count = 0;
+  const int64_t nt = G->ntraj;
+  if (nt == 0) return GF_OK;
+  if ((st = bind(ctx))) return st;
+  const size_t m = (size_t)nt;
+  if ((st = G->S.reserve(ctx, m * 8)) || (st = G->T.reserve(ctx, m * 8)) || (st = G->V.reserve(ctx, m * 8)) ||
+      (st = G->long_list.reserve(ctx, m * 4)) || (st = G->counters.reserve(ctx, 16)))
+    return st;
+  TStatsArgs a{};
+  a.x = pts->x; a.y = pts->y; a.ts = pts->ts;
+  a.perm = G->perm.as<uint32_t>();
+  a.seg_off = G->seg_off.as<uint32_t>();
+  a.ntraj = nt;
+  a.long_len = (uint32_t)G->long_len;
+  a.S = G->S.as<double>(); a.T = G->T.as<int64_t>(); a.V = G->V.as<double>();
+  a.long_list = G->long_list.as<uint32_t>();
+  a.long_count = G->counters.as<uint32_t>();
+  GF_HIP_CHECK(ctx, hipMemsetAsync(a.long_count, 0, 16, ctx->stream));
+  GF_HIP_CHECK(ctx, launch_tstats(ctx, a));
+  const int64_t* dk = G->keys.as<int64_t>();
+  const double *dS = a.S, *dV = a.V;
+  const int64_t* dT = a.T;
+  int64_t rows = nt;
+  if (nset > 0) {  // trajIDSet: the rows whose key is in the set, packed in order
+    std::vector<int64_t> set(id_set, id_set + nset);
+    std::sort(set.begin(), set.end());
+    set.erase(std::unique(set.begin(), set.end()), set.end());
+    if ((st = G->set.reserve(ctx, set.size() * 8)) || (st = G->sel.reserve(ctx, (m + 1) * 4)) ||
+        (st = G->srank.reserve(ctx, (m + 1) * 4)) || (st = G->ck.reserve(ctx, m * 8)) || (st = G->cS.reserve(ctx, m * 8)) ||
+        (st = G->cT.reserve(ctx, m * 8)) || (st = G->cV.reserve(ctx, m * 8)))
+      return st;
+    // (a pageable source: the copy has left `set` when the call returns)
+    GF_HIP_CHECK(ctx, hipMemcpy(G->set.p, set.data(), set.size() * 8, hipMemcpyHostToDevice));
+    uint32_t* sel = G->sel.as<uint32_t>();
+    uint32_t* srank = G->srank.as<uint32_t>();
+    GF_HIP_CHECK(ctx, launch_tstats_filter(ctx, a, dk, G->set.as<int64_t>(), (int64_t)set.size(), sel, srank, nullptr,
+                                           nullptr, nullptr, nullptr, 0));
+    if ((st = scan_u32(G, sel, nt, srank))) return st;
+    GF_HIP_CHECK(ctx, launch_tstats_filter(ctx, a, dk, nullptr, 0, sel, srank, G->ck.as<int64_t>(), G->cS.as<double>(),
+                                           G->cT.as<int64_t>(), G->cV.as<double>(), 1));
+    uint32_t r = 0;
+    GF_HIP_CHECK(ctx, hipMemcpyAsync(&r, srank + nt, sizeof r, hipMemcpyDeviceToHost, ctx->stream));
+    GF_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    rows = r;
+    dk = G->ck.as<int64_t>(); dS = G->cS.as<double>(); dT = G->cT.as<int64_t>(); dV = G->cV.as<double>();
+  }
+  const size_t wr = (size_t)std::min(rows, cap);
+  if ((st = read_back(ctx, keys, dk, wr)) || (st = read_back(ctx, spatial, dS, wr)) ||
+      (st = read_back(ctx, temporal, dT, wr)) || (st = read_back(ctx, speed, dV, wr)))
+    return st;
+  GF_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  *count = rows;
+  return GF_OK;
+}
+
+extern "C" int gf_traj_select(gf_traj_groups* G, const gf_points* pts, const uint64_t* bitmap, int64_t* keys, int64_t* off,
+                              int64_t cap_traj, double* x, double* y, int64_t* ts, uint32_t* idx, int64_t cap_pts,
+                              int64_t* ntraj_out, int64_t* npts_out) {
+  if (!G || !G->ctx) return GF_ERR_ARG;
+  gf_ctx* ctx = G->ctx;
+  if (!ntraj_out || !npts_out || cap_traj < 0 || cap_pts < 0 || (G->n > 0 && !bitmap))
+    return set_err(ctx, GF_ERR_ARG, "gf_traj_select: bad argument");
+  int st = check_traj_points(G, pts, "gf_traj_select");
+  if (st) return st;
+  *ntraj_out = 0;
+  *npts_out = 0;
+  if (off) off[0] = 0;
+  const int64_t nt = G->ntraj, n = G->n;
+  if (nt == 0) return GF_OK;
+  if ((st = bind(ctx))) return st;
+  const size_t m = (size_t)nt, np = (size_t)n;
+  if ((st = G->hit.reserve(ctx, (m + 1) * 4)) || (st = G->len.reserve(ctx, (m + 1) * 4)) ||
+      (st = G->row.reserve(ctx, (m + 1) * 4)) || (st = G->off.reserve(ctx, (m + 1) * 4)) ||
+      (st = G->okeys.reserve(ctx, m * 8)) || (st = G->ooff.reserve(ctx, (m + 1) * 4)) || (st = G->ox.reserve(ctx, np * 8)) ||
+      (st = G->oy.reserve(ctx, np * 8)) || (st = G->ots.reserve(ctx, np * 8)) || (st = G->oidx.reserve(ctx, np * 4)))
+    return st;
+  TrajSelectArgs a{};
+  a.x = pts->x; a.y = pts->y; a.ts = pts->ts;
+  a.n = n; a.ntraj = nt;
+  a.bitmap = bitmap;
+  a.did = G->did.as<uint32_t>();
+  a.sorted = G->kbuf[G->sorted_in].as<uint32_t>();
+  a.perm = G->perm.as<uint32_t>();
+  a.seg_off = G->seg_off.as<uint32_t>();
+  a.keys = G->keys.as<int64_t>();
+  a.hit = G->hit.as<uint32_t>();
+  a.len = G->len.as<uint32_t>();
+  a.row = G->row.as<uint32_t>();
+  a.off = G->off.as<uint32_t>();
+  a.okeys = G->okeys.as<int64_t>();
+  a.ooff = G->ooff.as<uint32_t>();
+  a.ox = G->ox.as<double>(); a.oy = G->oy.as<double>(); a.ots = G->ots.as<int64_t>(); a.oidx = G->oidx.as<uint32_t>();
+  GF_HIP_CHECK(ctx, hipMemsetAsync(a.hit, 0, (m + 1) * 4, ctx->stream));
+  GF_HIP_CHECK(ctx, launch_traj_select(ctx, 0, a));
+  if ((st = scan_u32(G, a.hit, nt, G->row.as<uint32_t>())) || (st = scan_u32(G, a.len, nt, G->off.as<uint32_t>())))
+    return st;
+  GF_HIP_CHECK(ctx, launch_traj_select(ctx, 1, a));
+  uint32_t tot[2] = {0, 0};
+  GF_HIP_CHECK(ctx, hipMemcpyAsync(&tot[0], a.row + nt, 4, hipMemcpyDeviceToHost, ctx->stream));
+  GF_HIP_CHECK(ctx, hipMemcpyAsync(&tot[1], a.off + nt, 4, hipMemcpyDeviceToHost, ctx->stream));
+  GF_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  const size_t wt = (size_t)std::min<int64_t>(tot[0], cap_traj), wp = (size_t)std::min<int64_t>(tot[1], cap_pts);
+  std::vector<uint32_t> ho;
+  if (off) ho.resize(wt + 1);
+  if ((st = read_back(ctx, keys, a.okeys, wt)) || (st = read_back(ctx, off ? ho.data() : nullptr, a.ooff, ho.size())) ||
+      (st = read_back(ctx, x, a.ox, wp)) || (st = read_back(ctx, y, a.oy, wp)) || (st = read_back(ctx, ts, a.ots, wp)) ||
+      (st = read_back(ctx, idx, a.oidx, wp)))
+    return st;
+  GF_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < ho.size(); ++i) off[i] = (int64_t)ho[i];
+  *ntraj_out = tot[0];
+  *npts_out = tot[1];
+  return GF_OK;
+}

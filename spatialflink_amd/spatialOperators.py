@@ -649,7 +649,207 @@ def synthetic_clustered(seed: int, n: int, minX: float, maxX: float, minY: float
     return x, y
 
 
+# ----------------------------------------------------------------------------------------
+# trajectories (the reference's t* operators: a window as the points of each objID in arrival order)
+# ----------------------------------------------------------------------------------------
+class TrajectoryGroups:
+    """gf_traj_groups of one window: the window grouped by objID on the device (stable, trajectories
+    in first-occurrence order).  regroup(window) reuses the device workspace for the next window."""
+
+    def __init__(self, window: PointWindow):
+        self.handle = C.c_void_p()
+        self.regroup(window)
+
+    def regroup(self, window: PointWindow):
+        self.window = window
+        self.ctx = _lib.context(window.x.device.index)
+        pts = window.c_struct()
+        _lib.check(_lib.lib().gf_traj_group(self.ctx.handle, C.byref(pts), C.byref(self.handle)), self.ctx.handle,
+                   "gf_traj_group")
+        nt, n = C.c_int64(), C.c_int64()
+        _lib.check(_lib.lib().gf_traj_groups_info(self.handle, C.byref(nt), C.byref(n)), None, "gf_traj_groups_info")
+        self.ntraj, self.n = nt.value, n.value
+        return self
+
+    def set_long_threshold(self, length: int):
+        """Testing / tuning: trajectories of at least `length` points take tStats' block path (0: default)."""
+        _lib.check(_lib.lib().gf_traj_groups_set_long_threshold(self.handle, int(length)), None,
+                   "gf_traj_groups_set_long_threshold")
+
+    def read(self):
+        """(keys int64[ntraj], seg_off int64[ntraj + 1], perm uint32[n]) on the host."""
+        keys = np.empty(self.ntraj, np.int64)
+        off = np.empty(self.ntraj + 1, np.int64)
+        perm = np.empty(self.n, np.uint32)
+        _lib.check(_lib.lib().gf_traj_groups_read(self.handle, keys.ctypes.data, off.ctypes.data, perm.ctypes.data),
+                   self.ctx.handle, "gf_traj_groups_read")
+        return keys, off, perm
+
+    def tstats(self, trajIDSet=(), cap=None):
+        """(count, keys, spatialLength, temporalLength, speed): at most `cap` rows (default: all)."""
+        ids = np.ascontiguousarray(np.asarray(list(trajIDSet), np.int64))
+        cap = self.ntraj if cap is None else int(cap)
+        keys, S, T, V = (np.empty(cap, np.int64), np.empty(cap, np.float64), np.empty(cap, np.int64),
+                         np.empty(cap, np.float64))
+        cnt = C.c_int64()
+        pts = self.window.c_struct()
+        st = _lib.lib().gf_tstats_run(self.handle, C.byref(pts), ids.ctypes.data if len(ids) else None, len(ids),
+                                      keys.ctypes.data, S.ctypes.data, T.ctypes.data, V.ctypes.data, cap, C.byref(cnt))
+        _lib.check(st, self.ctx.handle, "gf_tstats_run")
+        m = min(cnt.value, cap)
+        return cnt.value, keys[:m], S[:m], T[:m], V[:m]
+
+    def select(self, bitmap):
+        """Sub-trajectories of a device hit bitmap (torch int64 words) -> SubTrajectories."""
+        nt, n = self.ntraj, self.n
+        keys, off = np.empty(nt, np.int64), np.zeros(nt + 1, np.int64)
+        x, y, ts, idx = np.empty(n, np.float64), np.empty(n, np.float64), np.empty(n, np.int64), np.empty(n, np.uint32)
+        m, npts = C.c_int64(), C.c_int64()
+        pts = self.window.c_struct()
+        st = _lib.lib().gf_traj_select(self.handle, C.byref(pts), bitmap.data_ptr() if n else None, keys.ctypes.data,
+                                       off.ctypes.data, nt, x.ctypes.data, y.ctypes.data, ts.ctypes.data,
+                                       idx.ctypes.data, n, C.byref(m), C.byref(npts))
+        _lib.check(st, self.ctx.handle, "gf_traj_select")
+        k, q = m.value, npts.value
+        return SubTrajectories(self.window, keys[:k], off[:k + 1], x[:q], y[:q], ts[:q], idx[:q])
+
+    def close(self):
+        h = getattr(self, "handle", None)
+        if h and _lib._lib is not None:
+            _lib._lib.gf_traj_groups_destroy(h)
+            self.handle = C.c_void_p()
+
+    __del__ = close
+
+
+@dataclass
+class TStatsResult:
+    """TStatsQuery's rows Tuple4<objID, spatialLength, temporalLength, speed> (TStatsQuery.java:186-188)
+    as arrays, trajectories in first-occurrence order; objID holds the keys."""
+
+    window: PointWindow
+    objID: np.ndarray
+    spatialLength: np.ndarray
+    temporalLength: np.ndarray
+    speed: np.ndarray
+
+    def __len__(self):
+        return len(self.objID)
+
+    def objid_strings(self):
+        """The rows' objID Strings, through the window's dictionary."""
+        return self.window.objid_strings(self.objID)
+
+    def tuples(self):
+        return list(zip(self.objid_strings(), self.spatialLength.tolist(), self.temporalLength.tolist(),
+                        self.speed.tolist()))
+
+
+@dataclass
+class SubTrajectories:
+    """CSR of whole trajectories: trajectory j = objID[j], points [off[j], off[j+1]) of x, y, ts, idx
+    (idx = index in the window), in arrival order; trajectories in first-occurrence order."""
+
+    window: PointWindow
+    objID: np.ndarray
+    off: np.ndarray
+    x: np.ndarray
+    y: np.ndarray
+    ts: np.ndarray
+    idx: np.ndarray
+
+    def __len__(self):
+        return len(self.objID)
+
+    def objid_strings(self):
+        return self.window.objid_strings(self.objID)
+
+
+class PointTStatsQuery:
+    """tStats/PointTStatsQuery.java + TStatsQuery.java:148-189 -- window-based trajectory statistics:
+    per objID, over its points in arrival order, the travelled length, the time it took and their
+    quotient.  trajIDSet (objID Strings or keys; PointTStatsQuery.java:76-84): non-empty = only those."""
+
+    def __init__(self, conf: QueryConfiguration, index: UniformGrid = None):
+        self.conf = conf
+        self.index = index
+
+    def run(self, window: PointWindow, trajIDSet=()) -> TStatsResult:
+        if self.conf.getQueryType() != QueryType.WindowBased:
+            raise ValueError("Not yet support")
+        ids = _traj_id_keys(window, trajIDSet)
+        if ids is not None and len(ids) == 0:  # a non-empty set none of whose Strings the window can hold
+            e = np.empty(0)
+            return TStatsResult(window, e.astype(np.int64), e, e.astype(np.int64), e.copy())
+        g = TrajectoryGroups(window)
+        try:
+            _, keys, S, T, V = g.tstats(() if ids is None else ids)
+        finally:
+            g.close()
+        return TStatsResult(window, keys, S, T, V)
+
+
+def _traj_id_keys(window: PointWindow, trajIDSet):
+    """trajIDSet -> objID keys (None: no filter).  ints are keys; Strings are canonical decimals (their
+    value) or looked up among the window's own objID Strings (a String the window does not hold
+    cannot match and is dropped, never interned)."""
+    items = list(trajIDSet)
+    if not items:
+        return None
+    keys, strs = [], []
+    for it in items:
+        if isinstance(it, (int, np.integer)):
+            keys.append(int(it))
+        elif it is None:
+            keys.append(_lib.OBJID_NULL)
+        else:
+            v = _canonical_decimal(str(it))
+            if v is not None:
+                keys.append(v)
+            else:
+                strs.append(str(it))
+    if strs:
+        uk = np.unique(window.objID.cpu().numpy())
+        uk = uk[uk < _lib.OBJID_NUMERIC_MIN]
+        if len(uk):
+            want = set(strs)
+            keys += [int(k) for k, s in zip(uk.tolist(), window.objid_strings(uk)) if s in want]
+    return np.asarray(keys, np.int64)
+
+
+def _canonical_decimal(s: str):
+    """The key of a String that is exactly Long.toString(v), v in the numeric key range; else None."""
+    try:
+        v = int(s)
+    except ValueError:
+        return None
+    return v if str(v) == s and _lib.OBJID_NUMERIC_MIN <= v < _lib.OBJID_NUMERIC_END else None
+
+
+def group_by_objid(window: PointWindow):
+    """The window grouped by objID: (keys[ntraj], seg_off[ntraj + 1], perm[n]) -- trajectory t is
+    objID keys[t], its points perm[seg_off[t] : seg_off[t + 1]] in arrival order; trajectories in
+    first-occurrence order."""
+    g = TrajectoryGroups(window)
+    try:
+        return g.read()
+    finally:
+        g.close()
+
+
+def sub_trajectories(window: PointWindow, hits) -> SubTrajectories:
+    """Every trajectory with a hit point, whole (the assembly of the window-based tRange / tKnn /
+    tJoin).  hits: a RangeResult of `window`, or a device bitmap (torch int64 words, bit i = point i)."""
+    bitmap = hits.bitmap if isinstance(hits, RangeResult) else hits
+    g = TrajectoryGroups(window)
+    try:
+        return g.select(bitmap)
+    finally:
+        g.close()
+
+
 __all__ = [
+    "PointTStatsQuery", "TStatsResult", "SubTrajectories", "TrajectoryGroups", "group_by_objid", "sub_trajectories",
     "synthetic_clustered", "QueryType", "QueryConfiguration", "PointPointRangeQuery", "PointPolygonRangeQuery", "PointPointKNNQuery",
     "PointPointJoinQuery", "PointPolygonJoinQuery", "RangeResult", "KNNResult", "knn_merge_host", "assign_cells", "bucket_by_cell",
     "synthetic_uniform", "Point", "Polygon", "PointWindow", "knn_record_bytes", "decode_knn_record",
