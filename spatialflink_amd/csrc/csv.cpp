@@ -11,7 +11,7 @@
 #include <cstring>
 #include <string>
 
-#include "gf_internal.hpp"
+#include "gf_host.hpp"
 
 using namespace gf;
 
@@ -67,12 +67,12 @@ static int parse_text_lines(gf_ctx* ctx, gf_objid_dict* dict, const char* text, 
     // the dictionary worklist: at most one String per line
     if (grid_lines > 0 && (st = dict_reserve_batch(dict, (uint64_t)grid_lines, (uint64_t)grid_lines))) return st;
     CsvErr* err = (CsvErr*)(base + o_err);
-    ExpandState es;
-    if ((st = lookback_state(ctx, nseg, &es))) return st;
     // (the index's first block also resets the error slot and the dictionary counters)
-    GF_HIP_CHECK(ctx, launch_csv_nlindex(ctx->stream, text, len, nseg, (int64_t*)(base + o_nl), nl_cap,
-                                         (uint32_t*)(base + o_tot), es, err, dict->counters + 2));
-    ctx->expand_base += (unsigned long long)nseg;
+    if ((st = lookback_launch(ctx, nseg, nseg, "launch_csv_nlindex", [&](const ExpandState& es) {
+          return launch_csv_nlindex(ctx->stream, text, len, nseg, (int64_t*)(base + o_nl), nl_cap,
+                                    (uint32_t*)(base + o_tot), es, err, dict->counters + 2);
+        })))
+      return st;
     CsvArgs a = proto;
     a.text = text; a.len = len; a.nl = (int64_t*)(base + o_nl);
     a.nl_total = (const uint32_t*)(base + o_tot);

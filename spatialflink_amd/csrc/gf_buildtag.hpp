@@ -1,7 +1,7 @@
 // Build tag of one translation unit: which compile-time tuning / experiment defines it was built
 // with.  Included FIRST by every source of libgeoflink_hip.so, after `#define GF_TU_NAME <name>`,
 // so every GF_* macro seen here came from the compiler command line (the sources' own defaults
-// are set later, under #ifndef).  gf_build_info() (api.cpp) concatenates the tags of all units;
+// are set later, under #ifndef).  gf_build_info() (ctx.cpp) concatenates the tags of all units;
 // the smoke and the GPU suite require an empty list, so an experiment build cannot pass as the
 // product.
 //

@@ -525,7 +525,7 @@ struct CsvArgs {
 };
 hipError_t launch_csv_nlindex(hipStream_t st, const char* text, int64_t len, int64_t nseg, int64_t* nl, int64_t nl_cap,
                               uint32_t* total, const ExpandState& es, CsvErr* err, unsigned long long* dict_counters);
-int lookback_state(gf_ctx* ctx, int64_t blocks, ExpandState* es);  // api.cpp
+int lookback_state(gf_ctx* ctx, int64_t blocks, ExpandState* es);  // ctx.cpp
 hipError_t launch_csv_parse(gf_ctx* ctx, const CsvArgs& a);
 
 hipError_t launch_pane_bounds(hipStream_t s, const int64_t* ts, int64_t n, int64_t pane_ms, int64_t first_pane,
@@ -624,7 +624,7 @@ struct KnnLargeArgs {
 };
 hipError_t launch_knn_large(gf_ctx* ctx, int op, const KnnLargeArgs& a);
 constexpr int32_t kMaxKLarge = 1 << 24;  // largest k of the sorted (k > kMaxK) path
-// the exact record (status 0) of one window through the sorted path, any k (api.cpp)
+// the exact record (status 0) of one window through the sorted path, any k (knn.cpp)
 int knn_exact_record(gf_knn_plan* P, const gf_points* pts, void* result);
 
 hipError_t launch_knn_poly_sample(gf_ctx* ctx, const KnnPolyArgs& a);

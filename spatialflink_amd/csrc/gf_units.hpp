@@ -1,0 +1,11 @@
+// The translation units of libgeoflink_hip.so: X(<stem>, <ext>) names the file <stem>.<ext> in this
+// directory, whose GF_TU_NAME is <stem>_<ext> (gf_buildtag.hpp).  gf_build_info() and
+// gf_build_is_product() (ctx.cpp) walk this list, so a unit missing from it could carry experiment
+// defines unseen: tests/test_build_hygiene.py holds it, and the Makefile's SOURCES, equal to the
+// directory's *.cpp / *.hip files.
+#pragma once
+
+#define GF_UNITS(X)                                                                            \
+  X(ctx, cpp) X(grid, cpp) X(range, cpp) X(knn, cpp) X(join, cpp) X(window, cpp) X(comm, cpp)  \
+  X(sliding, cpp) X(csv, cpp) X(objid, cpp) X(traj, cpp) X(k_points, hip) X(k_knn, hip)        \
+  X(k_range, hip) X(k_join, hip) X(k_csv, hip) X(k_objid, hip) X(k_traj, hip)

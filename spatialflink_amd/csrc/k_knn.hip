@@ -798,7 +798,7 @@ __global__ __launch_bounds__(kSelT) void knn_select_kernel(KnnSelectArgs a) {
 // within r is kept (T = r, capacity >= window), then two stable LSD radix sorts over 32-bit key
 // fields of the candidate permutation -- (objID, d, idx) to keep each objID's first occurrence,
 // then the survivors by (d, objID, idx) -- and the first k are the record.  Kernels below; the
-// driver (api.cpp knn_large) reuses the K2 radix passes (k_points.hip).
+// driver (knn.cpp knn_large) reuses the K2 radix passes (k_points.hip).
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ int64_t large_count(const KnnLargeArgs& a, int which) {
   const int64_t c = (int64_t)a.cnt[which];

@@ -622,7 +622,7 @@ __global__ __launch_bounds__(NT, MINW) void radix_scatter_kernel(RadixArgs a) {
 // round of blocks; the steps' counts taken with LDS atomics, broadcast after the last step (no
 // wait per step) 63 vs 61 us.
 constexpr int kRowSortNT = 1024, kRowSortW = kRowSortNT / 64, kRowSortU = 32;
-constexpr int kRowSortCap = kRowSortNT * kRowSortU;  // >= api.cpp kRowSeg (checked there)
+constexpr int kRowSortCap = kRowSortNT * kRowSortU;  // >= grid.cpp kRowSeg (checked there)
 size_t radix_row_sort_lds_bytes() { return (size_t)kRowSortCap * 4 + (size_t)kRowSortW * kRadixMaxDigits * 2; }
 int radix_row_sort_cap() { return kRowSortCap; }
 

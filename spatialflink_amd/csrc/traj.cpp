@@ -12,7 +12,7 @@
 #include <cstring>
 #include <vector>
 
-#include "gf_internal.hpp"
+#include "gf_host.hpp"
 
 using namespace gf;
 
@@ -136,8 +136,7 @@ extern "C" int gf_traj_group(gf_ctx* ctx, const gf_points* pts, gf_traj_groups**
   int bits = 1;
   while (((uint64_t)1 << bits) < (uint64_t)ntraj) ++bits;
   const int passes = (bits + kRadixMaxBits - 1) / kRadixMaxBits, pbits = (bits + passes - 1) / passes;
-  const int64_t tiles = (n + radix_tile() - 1) / radix_tile();
-  const int blocks = (int)std::min<int64_t>(std::max<int64_t>(tiles / 4, 1), (int64_t)radix_max_blocks(ctx->num_cus));
+  const int blocks = radix_blocks(ctx, n);
   const int64_t mat = ((int64_t)1 << pbits) * blocks;
   if ((st = G->mat.reserve(ctx, sizeof(uint32_t) * (size_t)mat)) ||
       (st = G->mats.reserve(ctx, sizeof(uint32_t) * (size_t)(mat + 1))))

@@ -90,6 +90,27 @@ def test_every_unit_records_its_tag():
             assert "#include" not in text[:text.index("#define GF_TU_NAME")], f"{f}: tag must come first"
 
 
+def test_unit_list_and_makefile_sources_match_the_directory():
+    """gf_build_is_product() walks GF_UNITS (gf_units.hpp) and the Makefile links SOURCES: a unit
+    missing from either could carry experiment defines unseen, or not be built at all."""
+    import re
+
+    on_disk = {f for f in os.listdir(SRC) if f.endswith((".cpp", ".hip"))}
+    units = re.findall(r"\bX\(\s*(\w+)\s*,\s*(\w+)\s*\)", open(os.path.join(SRC, "gf_units.hpp")).read())
+    listed = [f"{stem}.{ext}" for stem, ext in units]
+    assert len(listed) == len(set(listed)), "a unit is listed twice"
+    assert set(listed) == on_disk
+    mk = open(os.path.join(ROOT, "Makefile")).read().replace("\\\n", " ")
+    sources = re.search(r"^SOURCES\s*:=(.*)$", mk, re.M).group(1).split()
+    assert all(s.startswith("$(SRC)/") for s in sources)
+    built = [s[len("$(SRC)/"):] for s in sources]
+    assert len(built) == len(set(built)), "a source is listed twice"
+    assert set(built) == on_disk
+    # the table is generated from the list, not kept by hand beside it
+    ctx = open(os.path.join(SRC, "ctx.cpp")).read()
+    assert "GF_UNITS(GF_UNIT_ROW)" in ctx and "GF_UNITS(GF_UNIT_DECL)" in ctx
+
+
 @pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "spatialflink_amd", "libgeoflink_hip.so")),
                     reason="library not built")
 def test_in_tree_library_is_the_product():
