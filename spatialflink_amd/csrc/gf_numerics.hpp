@@ -44,13 +44,21 @@ GF_HD int32_t jint(double v) {
 // or overflowing quotient) -- the correctly rounded division decides, as on the host.  Uniform
 // points take the exact division with probability ~1e-11 per point; the per-point fp64 division
 // (~11 vector instructions, a quarter-rate reciprocal among them) leaves the streaming loops.
-GF_HD int32_t cell_index(double v, double mn, double cl) {
-#ifdef __HIP_DEVICE_COMPILE__
+// cell_index_fast is that multiply with its guard band, host-callable so that the host tests can
+// hold it to the division: true when the guard band decides, and *cell is then the cell (an
+// integer in int range, still as a double); false when the division has to decide.
+GF_HD bool cell_index_fast(double v, double mn, double cl, double* cell) {
   const double t = v - mn, q = t * (1.0 / cl);
   const double e = fabs(q) * 0x1p-48 + 0x1p-1000;
   const double lo = floor(q - e);
-  if (lo == floor(q + e) && fabs(lo) < 2147483648.0) return (int32_t)lo;  // in range: no saturation
-  return jint(floor(t / cl));
+  *cell = lo;
+  return lo == floor(q + e) && fabs(lo) < 2147483648.0;  // in range: no saturation
+}
+GF_HD int32_t cell_index(double v, double mn, double cl) {
+#ifdef __HIP_DEVICE_COMPILE__
+  double c;
+  if (cell_index_fast(v, mn, cl, &c)) return (int32_t)c;
+  return jint(floor((v - mn) / cl));
 #else
   return jint(floor((v - mn) / cl));
 #endif
