@@ -684,7 +684,7 @@ struct KnnMergeArgs {
   KnnRecList list;
 };
 hipError_t launch_knn_fused(gf_ctx* ctx, const KnnScanArgs& a, const KnnSelectArgs& prev, int has_prev,
-                            int scan_blocks, int nt, const KnnMergeArgs* merge);
+                            int scan_blocks, int unroll, int nt, const KnnMergeArgs* merge);
 // gf_knn_enqueue with an optional window merge for the fused launch; *merged = 1 if it was
 // folded in (depth 2, a pending select, k <= kFusedMergeMaxK), else the caller launches it
 int knn_enqueue_merge(gf_knn_plan* P, const gf_points* pts, void* result, const KnnMergeArgs* merge, int* merged);
@@ -974,7 +974,7 @@ struct gf_knn_plan {
   void* tmp_result = nullptr;   // device record used by gf_knn_run / fallback
   void* host_result = nullptr;  // pinned
   int scan_blocks = 0;   // tuning: 0 = auto (4 blocks per CU)
-  int scan_unroll = 1;   // point pairs per lane per iteration (tools/tune_knn.py sweep)
+  int scan_unroll = 2;   // x tiles (point pairs per lane) per iteration (tools/tune_fused.py sweep)
   int scan_nt = 1;       // nontemporal loads
   int large = 0;         // k > kMaxK: every candidate within r, sorted (knn_large)
   // polygon query (gf_knn_ppoly_plan_create): device copy of the polygon, depth 1 only

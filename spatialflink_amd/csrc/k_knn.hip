@@ -7,9 +7,12 @@
 //               LDS (4096 log-spaced bins), flush to a global histogram, and the last block
 //               (atomic ticket) takes the upper edge of the bin holding the sample's k-th
 //               candidate (>= the window's k-th distance: the sample is a subset).
-//   knn_scan    the HBM-bound pass: 16 B/point (x, y), one compare per point against the exact
-//               prefilter s = dx*dx+dy*dy <= smax(T); survivors get the exact cell test (C u G)
-//               and are appended (d, idx, objID) with one atomic per wave.
+//   knn_scan    the HBM-bound pass, x first: every point's x streams (8 B/point); a lane reads y
+//               only if dx*dx <= smax(T) for one of its two points (exact: s >= dx*dx without
+//               contraction), a wave with no such lane issues no y load.  With T tight (a window
+//               2.1 wide, T ~ 0.004) that is ~6 % of y's 128-B segments.  Points in the band
+//               take the exact prefilter s = dx*dx+dy*dy <= smax(T); survivors get the exact
+//               cell test (C u G) and are appended (d, idx, objID) with one atomic per wave.
 //   knn_select  one 1024-thread block: candidates loaded at once, LDS histogram -> bins up to
 //               the k-th -> sort (in one wave's registers when <= 64, else LDS bitonic) ->
 //               objID dedupe -> first k; stores the next window's hint.
@@ -235,9 +238,42 @@ __device__ __forceinline__ void knn_scan_tile(const KnnScanArgs& a, const dbl2 (
   }
 }
 
-// Main loop: every wave runs the same number of full U-pair tiles with no bounds checks (loads
-// issued back to back from bumped pointers, counted waits); the remainder goes through a
-// checked one-pair-per-lane tail.  `bid` / `nblk`: this block's index among the scanning blocks.
+// x-first: a lane's y is read only if one of its two x lies inside the threshold band.
+// The build never contracts (-ffp-contract=off), so s = fl(fl(dx*dx) + fl(dy*dy)) >= fl(dx*dx)
+// for every dy (adding a non-negative term and rounding are both monotone): !(dx*dx <= sp)
+// implies !(s <= sp), for finite, infinite and NaN inputs and for both metrics.  The appended
+// candidates are therefore the same set as with both columns read; only their order may differ.
+__device__ __forceinline__ bool x_in_band(double qx, const dbl2& xv, double sp) {
+  const double dx0 = qx - xv.x, dx1 = qx - xv.y;
+  return (dx0 * dx0 <= sp) | (dx1 * dx1 <= sp);
+}
+
+// The y half of a tile: lanes outside the band keep y = NaN, which knn_pass rejects (NaN never
+// passes the prefilter); a wave with no lane in the band issues no y load and tests nothing.
+template <int METRIC, int U, int NT>
+__device__ __forceinline__ void knn_scan_tile_x(const KnnScanArgs& a, const dbl2 (&xv)[U], const dbl2* py,
+                                                int64_t p0, int64_t wstride, double sp, double T) {
+  bool bx[U], any = false;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    bx[u] = x_in_band(a.qx, xv[u], sp);
+    any |= bx[u];
+  }
+  if (__ballot(any) == 0) return;  // wave-uniform: most one-pair tiles once T is tight
+  dbl2 yv[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    yv[u].x = NAN; yv[u].y = NAN;
+    if (bx[u]) yv[u] = ld2<NT>(py + u * wstride);
+  }
+  knn_scan_tile<METRIC, U>(a, xv, yv, p0, wstride, sp, T);
+}
+
+// Main loop: every wave runs the same number of full U-pair tiles with no bounds checks.  Only
+// the x column streams (8 B/point); tile i+1's x loads are issued before tile i's band test, so
+// the dependent y loads of the lanes inside the band wait under the next tile's x traffic.  The
+// remainder goes through a checked one-pair-per-lane tail of the same form.  `bid` / `nblk`:
+// this block's index among the scanning blocks.
 template <int METRIC, int U, int NT>
 __device__ __forceinline__ void knn_scan_body(const KnnScanArgs& a, double sp, double T, int64_t bid, int64_t nblk) {
   const int lane = threadIdx.x & 63;
@@ -251,29 +287,45 @@ __device__ __forceinline__ void knn_scan_body(const KnnScanArgs& a, double sp, d
 #ifdef GF_TRACE
   if (threadIdx.x == 0) atomicMin(&a.st->tr[1], (unsigned long long)wall_clock64());
 #endif
-  for (int64_t it = 0; it < iters; ++it) {
-    dbl2 xv[U], yv[U];
+  dbl2 xv[U];
+  if (iters > 0) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      xv[u] = ld2<NT>(px + u * wstride);
-      yv[u] = ld2<NT>(py + u * wstride);
-    }
-    knn_scan_tile<METRIC, U>(a, xv, yv, pbeg + off + it * U * wstride, wstride, sp, T);
+    for (int u = 0; u < U; ++u) xv[u] = ld2<NT>(px + u * wstride);
+  }
+  for (int64_t it = 0; it < iters; ++it) {
+    dbl2 xn[U];
     px += U * wstride;
+    if (it + 1 < iters) {  // wave-uniform
+#pragma unroll
+      for (int u = 0; u < U; ++u) xn[u] = ld2<NT>(px + u * wstride);
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; ++u) { xn[u].x = NAN; xn[u].y = NAN; }
+    }
+    knn_scan_tile_x<METRIC, U, NT>(a, xv, py, pbeg + off + it * U * wstride, wstride, sp, T);
     py += U * wstride;
+#pragma unroll
+    for (int u = 0; u < U; ++u) xv[u] = xn[u];
   }
   const int64_t pend = (a.end + 1) >> 1;
   for (int64_t p = pbeg + iters * U * wstride + off; p - lane < pend; p += wstride) {
     const int64_t i = 2 * p;
-    dbl2 xv[1], yv[1];
-    if (i + 1 < a.end) {
-      xv[0] = *reinterpret_cast<const dbl2*>(a.x + i);
-      yv[0] = *reinterpret_cast<const dbl2*>(a.y + i);
+    dbl2 xt[1], yt[1];
+    const bool pair = i + 1 < a.end;
+    if (pair) {
+      xt[0] = *reinterpret_cast<const dbl2*>(a.x + i);
     } else {
-      xv[0].x = i < a.end ? a.x[i] : NAN; yv[0].x = i < a.end ? a.y[i] : NAN;
-      xv[0].y = NAN; yv[0].y = NAN;  // NaN never passes the prefilter
+      xt[0].x = i < a.end ? a.x[i] : NAN;
+      xt[0].y = NAN;
     }
-    knn_scan_tile<METRIC, 1>(a, xv, yv, p, wstride, sp, T);
+    yt[0].x = NAN; yt[0].y = NAN;  // NaN never passes the prefilter
+    const bool bx = x_in_band(a.qx, xt[0], sp);
+    if (__ballot(bx) == 0) continue;  // wave-uniform
+    if (bx) {
+      if (pair) yt[0] = *reinterpret_cast<const dbl2*>(a.y + i);
+      else yt[0].x = a.y[i];  // bx: x[i] is in the band, so i < a.end
+    }
+    knn_scan_tile<METRIC, 1>(a, xt, yt, p, wstride, sp, T);
   }
 #ifdef GF_TRACE
   __syncthreads();
@@ -1131,7 +1183,7 @@ __global__ __launch_bounds__(kMergeAnyT) void knn_merge_any_list_kernel(int32_t 
 // first, runs window i-1's select on the other lane while they stream.  One launch per window.
 // Sliding windows: with m.nrec > 0, block 0 then merges the window that closed with window i-1
 // (its pane records, the one just written included) into m.result -- no separate merge launch.
-template <int METRIC, int NT>
+template <int METRIC, int U, int NT>
 __global__ __launch_bounds__(kBlock) void knn_fused_kernel(KnnScanArgs a, KnnSelectArgs prev, int has_prev,
                                                            KnnMergeArgs m) {
   __shared__ SelLite L;
@@ -1155,22 +1207,31 @@ __global__ __launch_bounds__(kBlock) void knn_fused_kernel(KnnScanArgs a, KnnSel
     sp = s_prefilter(T, a.metric);
     if (blockIdx.x == 1 && threadIdx.x == 0) { a.st->T = T; a.st->s_pre = sp; }
   }
-  knn_scan_body<METRIC, 1, NT>(a, sp, T, blockIdx.x - 1, gridDim.x - 1);
+  knn_scan_body<METRIC, U, NT>(a, sp, T, blockIdx.x - 1, gridDim.x - 1);
 }
 
+template <int METRIC>
+static void launch_fused_u(gf_ctx* ctx, const dim3 g, const KnnScanArgs& a, const KnnSelectArgs& prev, int has_prev,
+                           const KnnMergeArgs& m, int unroll, int nt) {
+  const dim3 b(kBlock);
+#define GF_FUSED(U, N) hipLaunchKernelGGL((knn_fused_kernel<METRIC, U, N>), g, b, 0, ctx->stream, a, prev, has_prev, m)
+  if (nt) {
+    if (unroll <= 1) GF_FUSED(1, 1); else if (unroll == 2) GF_FUSED(2, 1); else GF_FUSED(4, 1);
+  } else {
+    if (unroll <= 1) GF_FUSED(1, 0); else if (unroll == 2) GF_FUSED(2, 0); else GF_FUSED(4, 0);
+  }
+#undef GF_FUSED
+}
+
+// unroll: x tiles per iteration, 1, 2 or 4 (larger values run 4)
 hipError_t launch_knn_fused(gf_ctx* ctx, const KnnScanArgs& a, const KnnSelectArgs& prev, int has_prev,
-                            int scan_blocks, int nt, const KnnMergeArgs* merge) {
+                            int scan_blocks, int unroll, int nt, const KnnMergeArgs* merge) {
   KTimer t(ctx, GF_K_KNN_SCAN);
-  const dim3 g(scan_blocks + 1), b(kBlock);
+  const dim3 g(scan_blocks + 1);
   KnnMergeArgs m{};
   if (merge && has_prev) m = *merge;
-  if (a.metric == 0) {
-    if (nt) hipLaunchKernelGGL((knn_fused_kernel<0, 1>), g, b, 0, ctx->stream, a, prev, has_prev, m);
-    else hipLaunchKernelGGL((knn_fused_kernel<0, 0>), g, b, 0, ctx->stream, a, prev, has_prev, m);
-  } else {
-    if (nt) hipLaunchKernelGGL((knn_fused_kernel<1, 1>), g, b, 0, ctx->stream, a, prev, has_prev, m);
-    else hipLaunchKernelGGL((knn_fused_kernel<1, 0>), g, b, 0, ctx->stream, a, prev, has_prev, m);
-  }
+  if (a.metric == 0) launch_fused_u<0>(ctx, g, a, prev, has_prev, m, unroll, nt);
+  else launch_fused_u<1>(ctx, g, a, prev, has_prev, m, unroll, nt);
   return hipGetLastError();
 }
 

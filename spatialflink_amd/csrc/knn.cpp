@@ -193,7 +193,7 @@ extern "C" int gf_knn_plan_set_index_base(gf_knn_plan* P, int64_t base) {
 
 static int scan_blocks_for(gf_knn_plan* P, int64_t n) {
   int blocks = P->scan_blocks;
-  if (blocks <= 0) {  // 4 blocks per CU measured best for the 1-pair nontemporal loop
+  if (blocks <= 0) {  // 4 blocks per CU: re-measured best for the x-first loop at 2 tiles per iteration
     blocks = stream_blocks(P->ctx, (n + 1) / 2);
     blocks = std::min(blocks, P->ctx->num_cus * 4);
   }
@@ -419,7 +419,7 @@ int gf::knn_enqueue_merge(gf_knn_plan* P, const gf_points* pts, void* result, co
                                    scan_blocks_for(P, (pts->n + 1) / 2), nullptr);
       else
         he = launch_knn_fused(ctx, scan_args(P, j, pts, 0, pts->n, sample ? 2 : 1), q, has_prev,
-                              scan_blocks_for(P, pts->n), P->scan_nt, merge);
+                              scan_blocks_for(P, pts->n), P->scan_unroll, P->scan_nt, merge);
       if (he != hipSuccess) { rc = hip_err(ctx, he, "launch_knn_fused"); break; }
       P->pq[P->npq++] = gf_knn_plan::Pend{j, result, P->idx_base, kseq};
     } while (0);
@@ -446,7 +446,8 @@ int gf::knn_enqueue_merge(gf_knn_plan* P, const gf_points* pts, void* result, co
                                              scan_blocks_for(P, (pts->n + 1) / 2), fold ? merge : nullptr));
     else
       GF_HIP_CHECK(ctx, launch_knn_fused(ctx, scan_args(P, j, pts, 0, pts->n, use_state), q, has_prev,
-                                         scan_blocks_for(P, pts->n), P->scan_nt, fold ? merge : nullptr));
+                                         scan_blocks_for(P, pts->n), P->scan_unroll, P->scan_nt,
+                                         fold ? merge : nullptr));
     *merged = fold ? 1 : 0;
     P->pend_lane = j;
     P->pend_result = result;
