@@ -77,18 +77,36 @@ class _PlanCache:
         self._destroy_name = destroy_name
         self.limit = int(limit)
         self._d = OrderedDict()
-        self._pinned = set()  # plans with state beyond their key (pipeline, capacity, a pane engine)
+        self._pinned = set()  # plans with state beyond their key (pipeline, capacity)
+        self._held = set()    # plans a pane engine (gf_*_sliding) borrows: never destroyed under it
+        self._orphans = {}    # held plans of a closed cache: destroyed when their engine lets go
 
     def pin(self, plan):
-        """Never evict `plan`: a plan with settings or pending pipelined work, or one a pane
-        engine (gf_*_sliding) holds, lives until it is unpinned or the operator closes."""
+        """Never evict `plan`: a plan with settings or pending pipelined work lives until it is
+        unpinned or the operator closes."""
         self._pinned.add(self._pv(plan))
 
     def unpin(self, plan):
-        """The holder of a pin is done with it (a pane engine closed): the plan is an ordinary
-        LRU entry again and is evicted if the cache is over its limit."""
+        """The plan is an ordinary LRU entry again and is evicted if the cache is over its limit."""
         self._pinned.discard(self._pv(plan))
         self._evict(None)
+
+    def hold(self, plan):
+        """A pane engine borrows `plan` (the engine dereferences it until it is destroyed): the
+        plan is not evicted, and close() leaves its destruction to release() -- the operator and
+        the engine may be finalized in either order (both die in one collected cycle)."""
+        self._held.add(self._pv(plan))
+
+    def release(self, plan):
+        """The pane engine is destroyed: the plan is an ordinary LRU entry again, or, if the cache
+        closed meanwhile, destroyed now."""
+        pv = self._pv(plan)
+        self._held.discard(pv)
+        orphan = self._orphans.pop(pv, None)
+        if orphan is not None:
+            self._destroy(orphan)
+        else:
+            self._evict(None)
 
     def get(self, key):
         plan = self._d.get(key)
@@ -107,7 +125,8 @@ class _PlanCache:
         over = len(self._d) - self.limit
         if over <= 0:
             return
-        victims = [k for k, p in self._d.items() if k != keep and self._pv(p) not in self._pinned][:over]
+        victims = [k for k, p in self._d.items()
+                   if k != keep and self._pv(p) not in self._pinned and self._pv(p) not in self._held][:over]
         for k in victims:
             self._destroy(self._d.pop(k))
 
@@ -125,7 +144,10 @@ class _PlanCache:
     def close(self):
         while self._d:
             _, p = self._d.popitem(last=False)
-            self._destroy(p)
+            if self._pv(p) in self._held:
+                self._orphans[self._pv(p)] = p
+            else:
+                self._destroy(p)
         self._pinned.clear()
 
 

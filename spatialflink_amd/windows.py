@@ -159,7 +159,7 @@ class SlidingKNNQuery:
         self.k = int(k)
         self.op = PointPointKNNQuery(conf, grid)
         self.ctx, self.plan = self.op.plan(device, queryPoint, queryRadius, k)
-        self.op._plans.pin(self.plan)  # the pane engine holds it
+        self.op._plans.hold(self.plan)  # the pane engine borrows it
         self.depth = int(pipeline)  # k > 256: the select is not fused, records complete in stream order
         _lib.check(_lib.lib().gf_knn_plan_set_pipeline(self.plan, self.depth), self.ctx.handle, "set_pipeline")
         h = C.c_void_p()
@@ -258,12 +258,12 @@ class SlidingKNNQuery:
         return self.pos
 
     def close(self):
-        """Destroy the pane engine and release its pin on the plan."""
+        """Destroy the pane engine and release its hold on the plan."""
         h = getattr(self, "handle", None)
         if h and _lib._lib is not None:
             _lib._lib.gf_knn_sliding_destroy(h)
             self.handle = None
-            self.op._plans.unpin(self.plan)
+            self.op._plans.release(self.plan)
 
     def __del__(self):
         self.close()
@@ -292,7 +292,7 @@ class SlidingRangeQuery:
 
         if self.handle is None:
             self.ctx, plan = self.op.plan(device, self.queries, self.r)
-            self.op._plans.pin(plan)
+            self.op._plans.hold(plan)
             self.plan = plan
             h = C.c_void_p()
             _lib.check(_lib.lib().gf_range_sliding_create(plan, self.geo.size, self.geo.slide, C.byref(h)),
@@ -361,11 +361,11 @@ class SlidingRangeQuery:
         return out
 
     def close(self):
-        """Destroy the pane engine and release its pin on the operator's plan."""
+        """Destroy the pane engine and release its hold on the operator's plan."""
         if getattr(self, "handle", None) is not None and _lib._lib is not None:
             _lib.lib().gf_range_sliding_destroy(self.handle)
             self.handle = None
-            self.op._plans.unpin(self.plan)
+            self.op._plans.release(self.plan)
 
     def __del__(self):
         self.close()

@@ -74,6 +74,37 @@ def test_plan_cache_keeps_pinned_plans(monkeypatch):
     assert len(c) == 2 and destroyed == [200, 201, 202, 203]  # the LRU unpinned ones go
 
 
+def test_plan_cache_leaves_held_plans_to_their_engine(monkeypatch):
+    """A plan a pane engine borrows (hold) is neither evicted nor destroyed by close(): the engine
+    dereferences it until the engine itself is destroyed, and the operator may be finalized first
+    (both die in one collected cycle).  release() destroys it then; before close() it only makes the
+    plan an ordinary LRU entry again."""
+    from spatialflink_amd import spatialOperators as so
+
+    destroyed = []
+    monkeypatch.setattr(so._PlanCache, "_destroy", lambda self, p: destroyed.append(p))
+    c = so._PlanCache("unused", limit=1)
+    c.put("a", 101)
+    c.hold(101)
+    c.put("b", 102)
+    c.put("c", 103)
+    assert destroyed == [102] and c.get("a") == 101
+    c.close()                      # the operator goes first
+    assert destroyed == [102, 103] and len(c) == 0
+    c.release(101)                 # the engine is gone: now the plan
+    assert destroyed == [102, 103, 101]
+    c.release(101)
+    assert destroyed == [102, 103, 101]
+    c = so._PlanCache("unused", limit=1)
+    c.put("a", 201)
+    c.hold(201)
+    c.put("b", 202)
+    c.release(201)                 # the engine goes first: back to the LRU bound
+    assert destroyed[3:] == [201] and c.get("b") == 202
+    c.close()
+    assert destroyed[3:] == [201, 202]
+
+
 def test_plan_cache_never_evicts_the_inserted_plan(monkeypatch):
     """With `limit` pinned plans, a new plan is the only unpinned entry: put() must keep it (the
     caller uses it next) and let the cache exceed its limit; unpinning restores the bound."""
