@@ -63,7 +63,8 @@ extern "C" {
 #define GF_K_TRAJ_GROUP  12 /* trajectories: the group-by-objID kernels (its radix passes count as GF_K_BUCKET) */
 #define GF_K_TSTATS      13 /* trajectories: tStats */
 #define GF_K_TRAJ_SELECT 14 /* trajectories: sub-trajectory extraction */
-#define GF_K_COUNT       15
+#define GF_K_TAGG        15 /* tAggregate: its own kernels (the grouping kernels count as GF_K_TRAJ_GROUP, the radix passes as GF_K_BUCKET) */
+#define GF_K_COUNT       16
 
 typedef struct gf_ctx gf_ctx;
 
@@ -667,6 +668,69 @@ int  gf_tstats_run(gf_traj_groups* g, const gf_points* pts, const int64_t* id_se
 int  gf_traj_select(gf_traj_groups* g, const gf_points* pts, const uint64_t* bitmap, int64_t* keys, int64_t* off,
                     int64_t cap_traj, double* x, double* y, int64_t* ts, uint32_t* idx, int64_t cap_pts,
                     int64_t* ntraj_out, int64_t* npts_out);
+
+/* ---- tAggregate: the windowed heatmap ------------------------------------------------------
+ * PointTAggregateQuery.java (QueryType.WindowBased, windowType "TIME") -> TAggregateQuery.java:498-613
+ * TimeWindowProcessFunction.process, for one device-resident window.  The reference keys the window
+ * by every point's cell-ID String and, per cell, walks the points in arrival order:
+ *   first point of an objID:  min = max = ts, length 0
+ *   repeat point:             min / max updated; length = max - min; sum follows the lengths;
+ *                             if (length > maxLen) maxLen, maxKey = length, objID   (strict)
+ *                             if (length < minLen) minLen, minKey = length, objID   (strict)
+ * The cell of a point is K1's (cx, cy) (HelperClass.assignGridCellID, Java (int) saturation, NaN -> 0).
+ * The reference's only filter is gridID != null, which every Point built with a grid passes: cells
+ * outside the grid are cells like any other.  The key here is the int32 pair (cx, cy); it differs
+ * from the "%05d%05d" String key only where an index needs more than five characters (Strings of
+ * different pairs can then coincide).  Per cell c, with D_c its distinct objID keys (any int64 is a
+ * legal key, as for gf_traj_group) and t_1 .. t_m the timestamps of objID o's points in c:
+ *   L_o = max t - min t;   e_o = |t_2 - t_1|, s_o = the window index of o's second point   (m >= 2)
+ *   f_o = the largest of s_o, the first index with ts == max t, the first index with ts == min t
+ *   count  = |D_c|                     multi = the number of o with m >= 2
+ *   sum    = the sum of L_o
+ *   minLen = min e_o over m >= 2,      minKey = the o with e_o == minLen and the smallest s_o
+ *   maxLen = max L_o over m >= 2,      maxKey = the o with L_o == maxLen and the smallest f_o
+ * (the running length of an objID never decreases, so the strict `<` is decided at second points --
+ * MIN is over e_o, not L_o, a quirk kept -- and the strict `>` by whoever reaches the final maximum
+ * first).  With multi == 0: minLen = INT64_MAX, maxLen = INT64_MIN (the reference's initial values),
+ * minKey = maxKey = 0.  Cells in the order of their first point in the window; inside a cell's ALL
+ * rows, objIDs in the order of their first point in that cell (Flink's order is unspecified; this one
+ * never depends on scheduling).  Timestamps >= 0 with sums inside int64; n < 2^32.  Results are
+ * identical from run to run.
+ * Not covered: the RealTime map function (TAggregateQuery.java:53-377, it reads the wall clock) and
+ * windowType "COUNT"; no JNI binding.
+ *
+ * gf_tagg_group (needs x, y, objID): the (cell, objID) grouping.  *out == NULL: a new object;
+ * otherwise that object (of the same context) is regrouped and its device workspace reused.  Sync.
+ * gf_tagg_run (pts: the grouped window; needs ts): the statistics.  Sync. */
+typedef struct gf_tagg gf_tagg;
+int  gf_tagg_group(gf_ctx* ctx, const gf_grid* grid, const gf_points* pts, gf_tagg** out);
+int  gf_tagg_run(gf_tagg* t, const gf_points* pts);
+void gf_tagg_destroy(gf_tagg* t);
+int  gf_tagg_info(const gf_tagg* t, int64_t* cells, int64_t* groups, int64_t* n);
+/* Testing / tuning: (cell, objID) groups of at least long_group points and cells of at least
+ * big_cell objIDs take the block-per-item paths (>= 1; 0 = the defaults, 2048 and 1024).  Takes effect
+ * at the next gf_tagg_run; results are identical for any values. */
+int  gf_tagg_set_thresholds(gf_tagg* t, int64_t long_group, int64_t big_cell);
+/* After gf_tagg_run, the per-cell table into HOST arrays (any may be NULL): *cells = all cells, at
+ * most cap written.  Sync. */
+int  gf_tagg_read_cells(gf_tagg* t, int32_t* cx, int32_t* cy, int64_t* count, int64_t* multi, int64_t* sum,
+                        int64_t* minLen, int64_t* minKey, int64_t* maxLen, int64_t* maxKey, int64_t cap, int64_t* cells);
+/* After gf_tagg_run, the ALL rows as CSR into HOST arrays (any may be NULL): cell j owns
+ * keys / len [off[j], off[j + 1]) = its {objID: L_o} map in first-point order.  *cells, *groups = the
+ * full sizes; off[0 .. min(cells, cap_cells)] and at most cap_groups keys / len are written.  Sync. */
+int  gf_tagg_read_all(gf_tagg* t, int64_t* off, int64_t* keys, int64_t* len, int64_t cap_cells, int64_t cap_groups,
+                      int64_t* cells, int64_t* groups);
+/* The emitted rows of one aggregate function from the per-cell table (pure host, no GPU): function
+ * is compared as equalsIgnoreCase.  *kind = 0 ALL (and any unknown name), 1 SUM, 2 AVG, 3 MIN, 4 MAX.
+ *   ALL  emit = 1, value = sum, key = 0 (the payload is the cell's gf_tagg_read_all map)
+ *   SUM  emit = sum > 0,   value = sum                                            key = 0 (the "" key)
+ *   AVG  emit = sum > 0,   value = Math.round((double)sum / (double)count)        key = 0
+ *   MIN  emit = multi > 0, value = minLen, key = minKey
+ *   MAX  emit = multi > 0, value = maxLen, key = maxKey
+ * Rows not emitted have value = key = 0.  minLen .. maxKey are read only by MIN / MAX. */
+int  gf_tagg_rows(const char* function, int64_t cells, const int64_t* count, const int64_t* multi, const int64_t* sum,
+                  const int64_t* minLen, const int64_t* minKey, const int64_t* maxLen, const int64_t* maxKey,
+                  uint8_t* emit, int64_t* value, int64_t* key, int32_t* kind);
 
 /* ---- pinned host memory ---------------------------------------------------------------
  * Mapped, portable host memory: kernels write kNN records straight into it (pass it as the

@@ -38,7 +38,7 @@ FLAG_GEOJSON_WAVE = 16
 FLAG_GEOJSON_CHECK = 32
 FLAG_JOIN_STREAM = 8
 (K_KNN_SCAN, K_KNN_SAMPLE, K_KNN_SELECT, K_RANGE_SCAN, K_ASSIGN, K_JOIN_PROBE, K_RANGE_TEST, K_JOIN_BUCKET,
- K_KNN_MERGE, K_CSV_PARSE, K_BUCKET, K_JOIN_COMPACT, K_TRAJ_GROUP, K_TSTATS, K_TRAJ_SELECT) = range(15)
+ K_KNN_MERGE, K_CSV_PARSE, K_BUCKET, K_JOIN_COMPACT, K_TRAJ_GROUP, K_TSTATS, K_TRAJ_SELECT, K_TAGG) = range(16)
 
 # Every symbol include/geoflink_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = [
@@ -67,6 +67,8 @@ EXPORTS = [
     "gf_knn_exchange_strings_batch", "gf_knn_exchange_group",
     "gf_traj_group", "gf_traj_groups_destroy", "gf_traj_groups_info", "gf_traj_groups_read",
     "gf_traj_groups_set_long_threshold", "gf_tstats_run", "gf_traj_select",
+    "gf_tagg_group", "gf_tagg_run", "gf_tagg_destroy", "gf_tagg_info", "gf_tagg_set_thresholds", "gf_tagg_read_cells",
+    "gf_tagg_read_all", "gf_tagg_rows",
 ]
 
 
@@ -243,6 +245,14 @@ def lib():
             "gf_traj_groups_set_long_threshold": ([P, i64], C.c_int),
             "gf_tstats_run": ([P, C.POINTER(GfPoints), P, i64, P, P, P, P, i64, pi64], C.c_int),
             "gf_traj_select": ([P, C.POINTER(GfPoints), P, P, P, i64, P, P, P, P, i64, pi64, pi64], C.c_int),
+            "gf_tagg_group": ([P, C.POINTER(GfGrid), C.POINTER(GfPoints), C.POINTER(P)], C.c_int),
+            "gf_tagg_run": ([P, C.POINTER(GfPoints)], C.c_int),
+            "gf_tagg_destroy": ([P], None),
+            "gf_tagg_info": ([P, pi64, pi64, pi64], C.c_int),
+            "gf_tagg_set_thresholds": ([P, i64, i64], C.c_int),
+            "gf_tagg_read_cells": ([P, P, P, P, P, P, P, P, P, P, i64, pi64], C.c_int),
+            "gf_tagg_read_all": ([P, P, P, P, i64, i64, pi64, pi64], C.c_int),
+            "gf_tagg_rows": ([C.c_char_p, i64, P, P, P, P, P, P, P, P, P, P, pi32], C.c_int),
         }
         for name, (argt, rest) in sig.items():
             if os.environ.get("GF_LIB_PATH") and not hasattr(L, name):

@@ -1,0 +1,58 @@
+// gf_group.hpp -- "group a device int64 key column" as the host units share it (traj.cpp holds the
+// bodies; the kernels are k_traj.hip's traj_* and k_points.hip's radix passes).  gf_traj_group is
+// group_keys over objID; tagg.cpp groups by cell, by objID and by the (cell, objID) pair with it.
+#pragma once
+
+#include "gf_host.hpp"
+
+namespace gf {
+
+// a grow-only device buffer
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  int reserve(gf_ctx* ctx, size_t need) {
+    if (need <= bytes) return GF_OK;
+    GF_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // queued work may still read the old one
+    if (p) hipFree(p);
+    p = nullptr;
+    bytes = 0;
+    GF_HIP_CHECK(ctx, hipMalloc(&p, need));
+    bytes = need;
+    return GF_OK;
+  }
+  void release() {
+    if (p) hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  template <class T>
+  T* as() const { return (T*)p; }
+};
+
+// The workspace and the result of one grouping: n items, ngroups distinct keys.
+//   keys[ngroups]        the distinct keys in first-occurrence order
+//   did[n]               dense id per item
+//   perm[n], seg_off[ngroups + 1], kbuf[sorted_in] = the sorted ids   (after group_sort_ids)
+struct KeyGroups {
+  int64_t n = 0, ngroups = 0;
+  DevBuf tkey, tfirst;       // the hash table (+ the empty marker's slot)
+  DevBuf kbuf[2], vbuf[2];   // radix ping-pong (n + 1 each); kbuf[1] = first-item flags, vbuf[1] = their scan
+  DevBuf did, perm, keys, seg_off, mat, mats, scan_tmp;
+  int sorted_in = 0;         // kbuf[sorted_in] = dense id per perm position
+  void release_groups() {
+    DevBuf* all[] = {&tkey, &tfirst, &kbuf[0], &kbuf[1], &vbuf[0], &vbuf[1], &did, &perm, &keys, &seg_off, &mat, &mats,
+                     &scan_tmp};
+    for (DevBuf* b : all) b->release();
+  }
+};
+
+int group_scan_u32(gf_ctx* ctx, KeyGroups& K, const uint32_t* in, int64_t L, uint32_t* out);
+// Dense ids of key[0, n) (device), 0 < n < 2^32: K.did, K.keys, K.ngroups; one mid-way host read (the
+// group count).  Enqueued on the context stream; the outputs are complete after a stream sync.
+int group_dense_ids(gf_ctx* ctx, KeyGroups& K, const int64_t* key, int64_t n, const char* who);
+// Stable LSD radix of the items by ids[0, n) (device; every id in [0, nids) occurs): K.perm, the sorted
+// ids (K.kbuf[K.sorted_in]) and K.seg_off[nids + 1].  Enqueued; ids may be K.did.
+int group_sort_ids(gf_ctx* ctx, KeyGroups& K, const uint32_t* ids, int64_t n, uint32_t nids);
+
+}  // namespace gf

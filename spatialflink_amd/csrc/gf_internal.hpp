@@ -597,6 +597,58 @@ struct TrajSelectArgs {
 // stage 0: hit + lens; 1: gather
 hipError_t launch_traj_select(gf_ctx* ctx, int stage, const TrajSelectArgs& a);
 
+// tAggregate (k_tagg.hip, tagg.cpp)
+constexpr int64_t kTaggLongLen = 2048;   // default: (cell, objID) groups of at least this many points take the block path
+constexpr int64_t kTaggBigCell = 1024;   // default: cells of at least this many groups take the block path
+struct TaggArgs {
+  // keys (stage 0 / 1)
+  const double* x;
+  const double* y;
+  int64_t n;
+  double minX, minY, cl;
+  int64_t* ckey;            // [n] pack(cx, cy)
+  const uint32_t* cid;      // [n] dense cell id per point
+  const uint32_t* oid;      // [n] dense objID id per point
+  int64_t* comp;            // [n] cid << 32 | oid
+  // per-group statistics (stage 2): group g = points perm[seg_off[g], seg_off[g + 1]) in window order
+  const int64_t* ts;
+  const uint32_t* perm;
+  const uint32_t* seg_off;
+  const uint32_t* sorted;   // [n] group id per perm position
+  const int64_t* gkeys;     // [ngroups] the groups' composite keys
+  const int64_t* okeys;     // [nobj] objID key of a dense objID id
+  int64_t ngroups;
+  uint32_t long_len;
+  uint32_t* g_cell;         // [ngroups] dense cell id
+  uint32_t* g_m;            // [ngroups] points
+  int64_t* g_key;           // [ngroups] objID key
+  int64_t* g_L;             // [ngroups] max ts - min ts
+  int64_t* g_e;             // [ngroups] |t2 - t1| (m >= 2)
+  uint32_t* g_f;            // [ngroups] window index at which L is first reached (m >= 2)
+  uint32_t* g_s;            // [ngroups] window index of the second point (m >= 2)
+  uint32_t* list;           // big cells
+  uint32_t* list_count;     // zero before the launch: stage 2 counts the long groups, stage 3 the listed cells
+  // per-cell aggregation (stage 3): cell c = groups gperm[cell_off[c], cell_off[c + 1])
+  const uint32_t* gperm;
+  const uint32_t* cell_off;
+  const int64_t* ckeys;     // [ncells] pack(cx, cy) of a dense cell id
+  int64_t ncells;
+  uint32_t big_cell;
+  int32_t* c_cx;
+  int32_t* c_cy;
+  int64_t* c_count;
+  int64_t* c_multi;
+  int64_t* c_sum;
+  int64_t* c_minLen;
+  int64_t* c_minKey;
+  int64_t* c_maxLen;
+  int64_t* c_maxKey;
+  int64_t* all_key;         // [ngroups] the ALL rows: objID key, length, in cell order
+  int64_t* all_len;
+};
+// stage 0: cell keys; 1: composite keys; 2: per-group statistics; 3: per-cell aggregation + ALL rows
+hipError_t launch_tagg(gf_ctx* ctx, int stage, const TaggArgs& a);
+
 hipError_t launch_knn_sample(gf_ctx* ctx, const KnnSampleArgs& a);
 hipError_t launch_knn_scan(gf_ctx* ctx, const KnnScanArgs& a, int blocks, int unroll, int nt);
 hipError_t launch_knn_select(gf_ctx* ctx, const KnnSelectArgs& a);

@@ -2,7 +2,8 @@
 // gf_tstats_run (TStatsQuery.java:154-188 per trajectory), gf_traj_select (sub-trajectories of a
 // hit bitmap).  The kernels are in k_traj.hip; the stable sort by dense trajectory id reuses the
 // LSD radix passes of k_points.hip.  The groups object owns its device workspace (grow-only) and is
-// reused across windows.
+// reused across windows.  The grouping itself -- dense ids of a device int64 key column, then the
+// stable sort by them -- is gf_group.hpp's, shared with tagg.cpp.
 #define GF_TU_NAME traj_cpp
 #include "gf_buildtag.hpp"  // first: records this unit's command-line defines
 
@@ -12,57 +13,111 @@
 #include <cstring>
 #include <vector>
 
-#include "gf_host.hpp"
+#include "gf_group.hpp"
 
 using namespace gf;
 
-namespace {
-// a grow-only device buffer
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  int reserve(gf_ctx* ctx, size_t need) {
-    if (need <= bytes) return GF_OK;
-    GF_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // queued work may still read the old one
-    if (p) hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    GF_HIP_CHECK(ctx, hipMalloc(&p, need));
-    bytes = need;
-    return GF_OK;
-  }
-  void release() {
-    if (p) hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  template <class T>
-  T* as() const { return (T*)p; }
-};
-}  // namespace
-
-struct gf_traj_groups {
+struct gf_traj_groups : KeyGroups {
   gf_ctx* ctx = nullptr;
-  int64_t n = 0, ntraj = 0;
+  int64_t ntraj = 0;
   int64_t long_len = kTrajLongLen;
-  // grouping
-  DevBuf tkey, tfirst;       // the hash table (+ the empty marker's slot)
-  DevBuf kbuf[2], vbuf[2];   // radix ping-pong (n + 1 each); kbuf[1] = first-point flags, vbuf[1] = their scan
-  DevBuf did, perm, keys, seg_off, mat, mats, scan_tmp;
-  int sorted_in = 0;         // kbuf[sorted_in] = dense id per perm position
   // tStats
   DevBuf S, T, V, long_list, counters, set, sel, srank, ck, cS, cT, cV;
   // sub-trajectories
   DevBuf hit, len, row, off, okeys, ooff, ox, oy, ots, oidx;
-  DevBuf* all[36] = {&tkey, &tfirst, &kbuf[0], &kbuf[1], &vbuf[0], &vbuf[1], &did, &perm, &keys, &seg_off, &mat, &mats,
-                     &scan_tmp, &S, &T, &V, &long_list, &counters, &set, &sel, &srank, &ck, &cS, &cT, &cV, &hit, &len,
+  DevBuf* all[23] = {&S, &T, &V, &long_list, &counters, &set, &sel, &srank, &ck, &cS, &cT, &cV, &hit, &len,
                      &row, &off, &okeys, &ooff, &ox, &oy, &ots, &oidx, nullptr};
 };
 
 static int scan_u32(gf_traj_groups* G, const uint32_t* in, int64_t L, uint32_t* out) {
-  gf_ctx* ctx = G->ctx;
-  if (int st = G->scan_tmp.reserve(ctx, scan_tmp_elems(L) * sizeof(uint32_t))) return st;
-  GF_HIP_CHECK(ctx, launch_exclusive_scan(ctx->stream, in, L, out, G->scan_tmp.as<uint32_t>()));
+  return group_scan_u32(G->ctx, *G, in, L, out);
+}
+
+// ---- gf_group.hpp: the grouping of a device int64 key column ----------------------------------
+int gf::group_scan_u32(gf_ctx* ctx, KeyGroups& K, const uint32_t* in, int64_t L, uint32_t* out) {
+  if (int st = K.scan_tmp.reserve(ctx, scan_tmp_elems(L) * sizeof(uint32_t))) return st;
+  GF_HIP_CHECK(ctx, launch_exclusive_scan(ctx->stream, in, L, out, K.scan_tmp.as<uint32_t>()));
+  return GF_OK;
+}
+
+int gf::group_dense_ids(gf_ctx* ctx, KeyGroups& K, const int64_t* key, int64_t n, const char* who) {
+  int st = GF_OK;
+  K.n = n;
+  K.ngroups = 0;
+  uint64_t slots = 64;
+  while (slots < 2 * (uint64_t)n) slots <<= 1;
+  const size_t w = sizeof(uint32_t) * (size_t)(n + 1);
+  if ((st = K.tkey.reserve(ctx, (slots + 1) * sizeof(unsigned long long))) ||
+      (st = K.tfirst.reserve(ctx, (slots + 1) * sizeof(uint32_t))) || (st = K.kbuf[1].reserve(ctx, w)) ||
+      (st = K.vbuf[1].reserve(ctx, w)) || (st = K.did.reserve(ctx, w)))
+    return st;
+  TrajGroupArgs a{};
+  a.t.key = K.tkey.as<unsigned long long>();
+  a.t.first = K.tfirst.as<uint32_t>();
+  a.t.mask = slots - 1;
+  a.objID = key;
+  a.n = n;
+  a.flag = K.kbuf[1].as<uint32_t>();
+  a.rank = K.vbuf[1].as<uint32_t>();
+  a.did = K.did.as<uint32_t>();
+  hipError_t e = launch_traj_group(ctx, 0, a);
+  if (e != hipSuccess) return hip_err(ctx, e, "traj insert");
+  if ((st = group_scan_u32(ctx, K, a.flag, n, K.vbuf[1].as<uint32_t>()))) return st;
+  // the group count sizes the outputs and the sort's digits: the call's one mid-way host read
+  uint32_t ng = 0;
+  e = hipMemcpyAsync(&ng, a.rank + n, sizeof ng, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) return hip_err(ctx, e, "traj count");
+  if (ng < 1 || (int64_t)ng > n) return set_err(ctx, GF_ERR_HIP, std::string(who) + ": inconsistent trajectory count");
+  if ((st = K.keys.reserve(ctx, sizeof(int64_t) * (size_t)ng))) return st;
+  a.keys = K.keys.as<int64_t>();
+  a.ntraj = ng;
+  if ((e = launch_traj_group(ctx, 1, a)) != hipSuccess) return hip_err(ctx, e, "traj assign");
+  K.ngroups = ng;
+  return GF_OK;
+}
+
+int gf::group_sort_ids(gf_ctx* ctx, KeyGroups& K, const uint32_t* ids, int64_t n, uint32_t nids) {
+  int st = GF_OK;
+  const size_t w = sizeof(uint32_t) * (size_t)(n + 1);
+  if ((st = K.kbuf[0].reserve(ctx, w)) || (st = K.kbuf[1].reserve(ctx, w)) || (st = K.vbuf[0].reserve(ctx, w)) ||
+      (st = K.vbuf[1].reserve(ctx, w)) || (st = K.perm.reserve(ctx, w)) ||
+      (st = K.seg_off.reserve(ctx, sizeof(uint32_t) * ((size_t)nids + 1))))
+    return st;
+  // stable LSD radix over the dense ids (ids < nids): digits of <= kRadixMaxBits bits
+  int bits = 1;
+  while (((uint64_t)1 << bits) < (uint64_t)nids) ++bits;
+  const int passes = (bits + kRadixMaxBits - 1) / kRadixMaxBits, pbits = (bits + passes - 1) / passes;
+  const int blocks = radix_blocks(ctx, n);
+  const int64_t mat = ((int64_t)1 << pbits) * blocks;
+  if ((st = K.mat.reserve(ctx, sizeof(uint32_t) * (size_t)mat)) ||
+      (st = K.mats.reserve(ctx, sizeof(uint32_t) * (size_t)(mat + 1))))
+    return st;
+  RadixArgs r{};
+  r.tile = radix_tile();
+  r.n = n;
+  r.bits = pbits;
+  r.nblk = blocks;
+  r.M = K.mat.as<uint32_t>();
+  r.Ms = K.mats.as<uint32_t>();
+  hipError_t e;
+  for (int p = 0; p < passes; ++p) {
+    r.kin = p == 0 ? ids : K.kbuf[(p - 1) & 1].as<uint32_t>();
+    r.vin = p == 0 ? nullptr : K.vbuf[(p - 1) & 1].as<uint32_t>();  // pass 0: the index is the position
+    r.kout = K.kbuf[p & 1].as<uint32_t>();
+    r.vout = p == passes - 1 ? K.perm.as<uint32_t>() : K.vbuf[p & 1].as<uint32_t>();
+    r.shift = p * pbits;
+    if ((e = launch_radix(ctx, 0, r, blocks)) != hipSuccess) return hip_err(ctx, e, "traj radix histogram");
+    if ((st = group_scan_u32(ctx, K, r.M, mat, K.mats.as<uint32_t>()))) return st;
+    if ((e = launch_radix(ctx, 1, r, blocks)) != hipSuccess) return hip_err(ctx, e, "traj radix scatter");
+  }
+  K.sorted_in = (passes - 1) & 1;
+  TrajGroupArgs a{};
+  a.n = n;
+  a.ntraj = nids;
+  a.sorted = K.kbuf[K.sorted_in].as<uint32_t>();
+  a.seg_off = K.seg_off.as<uint32_t>();
+  if ((e = launch_traj_group(ctx, 2, a)) != hipSuccess) return hip_err(ctx, e, "traj bounds");
   return GF_OK;
 }
 
@@ -85,12 +140,12 @@ extern "C" int gf_traj_group(gf_ctx* ctx, const gf_points* pts, gf_traj_groups**
   G->ctx = ctx;
   auto fail = [&](int code) {
     if (fresh) gf_traj_groups_destroy(G);
-    else G->n = G->ntraj = 0;
+    else G->n = G->ntraj = G->ngroups = 0;
     return code;
   };
   const int64_t n = pts->n;
   G->n = n;
-  G->ntraj = 0;
+  G->ntraj = G->ngroups = 0;
   if ((st = G->seg_off.reserve(ctx, sizeof(uint32_t)))) return fail(st);
   if (n == 0) {
     hipError_t e = hipMemsetAsync(G->seg_off.p, 0, sizeof(uint32_t), ctx->stream);
@@ -99,70 +154,12 @@ extern "C" int gf_traj_group(gf_ctx* ctx, const gf_points* pts, gf_traj_groups**
     *out = G;
     return GF_OK;
   }
-  uint64_t slots = 64;
-  while (slots < 2 * (uint64_t)n) slots <<= 1;
-  const size_t w = sizeof(uint32_t) * (size_t)(n + 1);
-  if ((st = G->tkey.reserve(ctx, (slots + 1) * sizeof(unsigned long long))) ||
-      (st = G->tfirst.reserve(ctx, (slots + 1) * sizeof(uint32_t))) || (st = G->kbuf[0].reserve(ctx, w)) ||
-      (st = G->kbuf[1].reserve(ctx, w)) || (st = G->vbuf[0].reserve(ctx, w)) || (st = G->vbuf[1].reserve(ctx, w)) ||
-      (st = G->did.reserve(ctx, w)) || (st = G->perm.reserve(ctx, w)))
+  if ((st = group_dense_ids(ctx, *G, pts->objID, n, "gf_traj_group")) ||
+      (st = group_sort_ids(ctx, *G, G->did.as<uint32_t>(), n, (uint32_t)G->ngroups)))
     return fail(st);
-  TrajGroupArgs a{};
-  a.t.key = G->tkey.as<unsigned long long>();
-  a.t.first = G->tfirst.as<uint32_t>();
-  a.t.mask = slots - 1;
-  a.objID = pts->objID;
-  a.n = n;
-  a.flag = G->kbuf[1].as<uint32_t>();
-  a.rank = G->vbuf[1].as<uint32_t>();
-  a.did = G->did.as<uint32_t>();
-  hipError_t e = launch_traj_group(ctx, 0, a);
-  if (e != hipSuccess) return fail(hip_err(ctx, e, "traj insert"));
-  if ((st = scan_u32(G, a.flag, n, G->vbuf[1].as<uint32_t>()))) return fail(st);
-  // the trajectory count sizes the outputs and the sort's digits: the call's one mid-way host read
-  uint32_t ntraj = 0;
-  e = hipMemcpyAsync(&ntraj, a.rank + n, sizeof ntraj, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) return fail(hip_err(ctx, e, "traj count"));
-  if (ntraj < 1 || (int64_t)ntraj > n) return fail(set_err(ctx, GF_ERR_HIP, "gf_traj_group: inconsistent trajectory count"));
-  if ((st = G->keys.reserve(ctx, sizeof(int64_t) * (size_t)ntraj)) ||
-      (st = G->seg_off.reserve(ctx, sizeof(uint32_t) * ((size_t)ntraj + 1))))
-    return fail(st);
-  a.keys = G->keys.as<int64_t>();
-  a.ntraj = ntraj;
-  a.seg_off = G->seg_off.as<uint32_t>();
-  if ((e = launch_traj_group(ctx, 1, a)) != hipSuccess) return fail(hip_err(ctx, e, "traj assign"));
-  // stable LSD radix over the dense ids (ids < ntraj): digits of <= kRadixMaxBits bits
-  int bits = 1;
-  while (((uint64_t)1 << bits) < (uint64_t)ntraj) ++bits;
-  const int passes = (bits + kRadixMaxBits - 1) / kRadixMaxBits, pbits = (bits + passes - 1) / passes;
-  const int blocks = radix_blocks(ctx, n);
-  const int64_t mat = ((int64_t)1 << pbits) * blocks;
-  if ((st = G->mat.reserve(ctx, sizeof(uint32_t) * (size_t)mat)) ||
-      (st = G->mats.reserve(ctx, sizeof(uint32_t) * (size_t)(mat + 1))))
-    return fail(st);
-  RadixArgs r{};
-  r.tile = radix_tile();
-  r.n = n;
-  r.bits = pbits;
-  r.nblk = blocks;
-  r.M = G->mat.as<uint32_t>();
-  r.Ms = G->mats.as<uint32_t>();
-  for (int p = 0; p < passes; ++p) {
-    r.kin = p == 0 ? G->did.as<uint32_t>() : G->kbuf[(p - 1) & 1].as<uint32_t>();
-    r.vin = p == 0 ? nullptr : G->vbuf[(p - 1) & 1].as<uint32_t>();  // pass 0: the index is the position
-    r.kout = G->kbuf[p & 1].as<uint32_t>();
-    r.vout = p == passes - 1 ? G->perm.as<uint32_t>() : G->vbuf[p & 1].as<uint32_t>();
-    r.shift = p * pbits;
-    if ((e = launch_radix(ctx, 0, r, blocks)) != hipSuccess) return fail(hip_err(ctx, e, "traj radix histogram"));
-    if ((st = scan_u32(G, r.M, mat, G->mats.as<uint32_t>()))) return fail(st);
-    if ((e = launch_radix(ctx, 1, r, blocks)) != hipSuccess) return fail(hip_err(ctx, e, "traj radix scatter"));
-  }
-  G->sorted_in = (passes - 1) & 1;
-  a.sorted = G->kbuf[G->sorted_in].as<uint32_t>();
-  if ((e = launch_traj_group(ctx, 2, a)) != hipSuccess) return fail(hip_err(ctx, e, "traj bounds"));
-  if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(hip_err(ctx, e, "gf_traj_group"));
-  G->ntraj = ntraj;
+  hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) return fail(hip_err(ctx, e, "gf_traj_group"));
+  G->ntraj = G->ngroups;
   *out = G;
   return GF_OK;
 }
@@ -173,6 +170,7 @@ extern "C" void gf_traj_groups_destroy(gf_traj_groups* G) {
     hipSetDevice(G->ctx->device);
     hipStreamSynchronize(G->ctx->stream);
   }
+  G->release_groups();
   for (DevBuf** b = G->all; *b; ++b) (*b)->release();
   delete G;
 }

@@ -23,7 +23,7 @@ from enum import Enum
 import numpy as np
 
 from . import _lib
-from .spatialIndices import UniformGrid
+from .spatialIndices import UniformGrid, generateCellIDStr
 from .spatialObjects import Point, PointWindow, Polygon, PolygonSet
 
 
@@ -870,7 +870,165 @@ def sub_trajectories(window: PointWindow, hits) -> SubTrajectories:
         g.close()
 
 
+# ----------------------------------------------------------------------------------------
+# tAggregate (the windowed heatmap: per grid cell, how long each objID stayed)
+# ----------------------------------------------------------------------------------------
+TAGG_KINDS = ("ALL", "SUM", "AVG", "MIN", "MAX")
+
+
+def tagg_rows(aggregateFunction: str, table):
+    """gf_tagg_rows (pure host): the emitted rows of one aggregate function from a per-cell table (the
+    dict of TAggregateGroups.cells()) -> (kind, emit bool[cells], value int64[cells], key int64[cells])."""
+    cols = {k: np.ascontiguousarray(table[k], np.int64) for k in
+            ("count", "multi", "sum", "minLen", "minKey", "maxLen", "maxKey")}
+    m = len(cols["count"])
+    emit, value, key = np.zeros(m, np.uint8), np.zeros(m, np.int64), np.zeros(m, np.int64)
+    kind = C.c_int32()
+    st = _lib.lib().gf_tagg_rows(str(aggregateFunction).encode(), m, *(cols[k].ctypes.data for k in
+                                 ("count", "multi", "sum", "minLen", "minKey", "maxLen", "maxKey")),
+                                 emit.ctypes.data, value.ctypes.data, key.ctypes.data, C.byref(kind))
+    _lib.check(st, None, "gf_tagg_rows")
+    return TAGG_KINDS[kind.value], emit.astype(bool), value, key
+
+
+class TAggregateGroups:
+    """gf_tagg of one window: the window grouped by (cell, objID) on the device (stable; cells and,
+    inside a cell, objIDs in first-occurrence order).  regroup(window, grid) reuses the device
+    workspace for the next window; run() computes the statistics."""
+
+    def __init__(self, window: PointWindow, grid: UniformGrid):
+        self.handle = C.c_void_p()
+        self.regroup(window, grid)
+
+    def regroup(self, window: PointWindow, grid: UniformGrid):
+        self.window = window
+        self.ctx = _lib.context(window.x.device.index)
+        pts = window.c_struct()
+        _lib.check(_lib.lib().gf_tagg_group(self.ctx.handle, C.byref(grid.c_grid), C.byref(pts), C.byref(self.handle)),
+                   self.ctx.handle, "gf_tagg_group")
+        c, g, n = C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check(_lib.lib().gf_tagg_info(self.handle, C.byref(c), C.byref(g), C.byref(n)), None, "gf_tagg_info")
+        self.ncells, self.ngroups, self.n = c.value, g.value, n.value
+        return self
+
+    def set_thresholds(self, long_group: int = 0, big_cell: int = 0):
+        """Testing / tuning: groups of at least `long_group` points and cells of at least `big_cell`
+        objIDs take the block paths at the next run() (0: the defaults)."""
+        _lib.check(_lib.lib().gf_tagg_set_thresholds(self.handle, int(long_group), int(big_cell)), None,
+                   "gf_tagg_set_thresholds")
+
+    def run(self):
+        pts = self.window.c_struct()
+        _lib.check(_lib.lib().gf_tagg_run(self.handle, C.byref(pts)), self.ctx.handle, "gf_tagg_run")
+        return self
+
+    def cells(self):
+        """The per-cell table on the host: dict of cx, cy (int32) and count, multi, sum, minLen, minKey,
+        maxLen, maxKey (int64), one entry per cell."""
+        m = self.ncells
+        t = {k: np.empty(m, np.int32) for k in ("cx", "cy")}
+        t.update({k: np.empty(m, np.int64) for k in ("count", "multi", "sum", "minLen", "minKey", "maxLen", "maxKey")})
+        got = C.c_int64()
+        st = _lib.lib().gf_tagg_read_cells(self.handle, *(a.ctypes.data for a in t.values()), m, C.byref(got))
+        _lib.check(st, self.ctx.handle, "gf_tagg_read_cells")
+        return t
+
+    def all_rows(self):
+        """The ALL maps as CSR on the host: (off int64[cells + 1], keys int64[groups], len int64[groups])."""
+        off = np.zeros(self.ncells + 1, np.int64)
+        keys, ln = np.empty(self.ngroups, np.int64), np.empty(self.ngroups, np.int64)
+        c, g = C.c_int64(), C.c_int64()
+        st = _lib.lib().gf_tagg_read_all(self.handle, off.ctypes.data, keys.ctypes.data, ln.ctypes.data, self.ncells,
+                                         self.ngroups, C.byref(c), C.byref(g))
+        _lib.check(st, self.ctx.handle, "gf_tagg_read_all")
+        return off, keys, ln
+
+    def close(self):
+        h = getattr(self, "handle", None)
+        if h and _lib._lib is not None:
+            _lib._lib.gf_tagg_destroy(h)
+            self.handle = C.c_void_p()
+
+    __del__ = close
+
+
+@dataclass
+class TAggregateResult:
+    """The emitted rows of TimeWindowProcessFunction (TAggregateQuery.java:498-613) as arrays, one row
+    per emitted cell, cells in the order of their first point in the window: (cx, cy), count, and the
+    payload -- ALL: the cell's {objID: length} map as CSR (off, keys, lens; objIDs in the order of
+    their first point in the cell); SUM / AVG: value; MIN / MAX: (key, value).  start / end are the
+    window's, carried through."""
+
+    window: PointWindow
+    kind: str
+    cx: np.ndarray
+    cy: np.ndarray
+    count: np.ndarray
+    value: np.ndarray
+    key: np.ndarray
+    off: np.ndarray
+    keys: np.ndarray
+    lens: np.ndarray
+    start: int = 0
+    end: int = 0
+
+    def __len__(self):
+        return len(self.cx)
+
+    def cell_ids(self):
+        """The rows' cell-ID Strings ("%05d%05d", HelperClass.java:118-120)."""
+        return [generateCellIDStr(a, b) for a, b in zip(self.cx.tolist(), self.cy.tolist())]
+
+    def tuples(self):
+        """Tuple5<cellID, count, winStart, winEnd, map>: objID Strings through the window's dictionary;
+        SUM / AVG carry the reference's "" key."""
+        ids = self.cell_ids()
+        if self.kind == "ALL":
+            names = self.window.objid_strings(self.keys) if len(self.keys) else []
+            lens, off = self.lens.tolist(), self.off.tolist()
+            maps = [OrderedDict(zip(names[off[j]:off[j + 1]], lens[off[j]:off[j + 1]])) for j in range(len(ids))]
+        elif self.kind in ("SUM", "AVG"):
+            maps = [{"": v} for v in self.value.tolist()]
+        else:
+            names = self.window.objid_strings(self.key) if len(self.key) else []
+            maps = [{s: v} for s, v in zip(names, self.value.tolist())]
+        return [(i, c, self.start, self.end, m) for i, c, m in zip(ids, self.count.tolist(), maps)]
+
+
+class PointTAggregateQuery:
+    """tAggregate/PointTAggregateQuery.java + TAggregateQuery.java:498-613 -- the windowed heatmap: per
+    grid cell of the window, the objIDs seen there, how long each stayed (max ts - min ts of its points
+    in the cell) and ALL / SUM / AVG / MIN / MAX of those stays (names as equalsIgnoreCase; any other
+    name behaves as ALL).  WindowBased with the TIME window only: the RealTime variant reads the wall
+    clock and COUNT windows are per-cell streams; both raise as unsupported."""
+
+    def __init__(self, conf: QueryConfiguration, index: UniformGrid = None):
+        self.conf = conf
+        self.index = index
+
+    def run(self, window: PointWindow, aggregateFunction: str, windowType: str = "TIME", groups=None) -> TAggregateResult:
+        if self.conf.getQueryType() != QueryType.WindowBased or str(windowType).upper() == "COUNT":
+            raise ValueError("Not yet support")
+        if self.index is None:
+            raise ValueError("PointTAggregateQuery needs the grid")
+        g = groups.regroup(window, self.index) if groups is not None else TAggregateGroups(window, self.index)
+        try:
+            t = g.run().cells()
+            kind, emit, value, key = tagg_rows(aggregateFunction, t)
+            off = np.zeros(1, np.int64)
+            keys = lens = np.empty(0, np.int64)
+            if kind == "ALL":
+                off, keys, lens = g.all_rows()
+        finally:
+            if groups is None:
+                g.close()
+        return TAggregateResult(window, kind, t["cx"][emit], t["cy"][emit], t["count"][emit], value[emit], key[emit],
+                                off, keys, lens, window.start, window.end)
+
+
 __all__ = [
+    "PointTAggregateQuery", "TAggregateResult", "TAggregateGroups", "tagg_rows",
     "PointTStatsQuery", "TStatsResult", "SubTrajectories", "TrajectoryGroups", "group_by_objid", "sub_trajectories",
     "synthetic_clustered", "QueryType", "QueryConfiguration", "PointPointRangeQuery", "PointPolygonRangeQuery", "PointPointKNNQuery",
     "PointPointJoinQuery", "PointPolygonJoinQuery", "RangeResult", "KNNResult", "knn_merge_host", "assign_cells", "bucket_by_cell",
