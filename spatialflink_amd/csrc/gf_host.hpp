@@ -38,6 +38,17 @@ struct Arena {
   int nslots = 0;
 };
 
+// Launchers take ctx->stream: work for another stream swaps it in for a scope, and every exit
+// from the scope puts the caller's stream back.
+struct StreamScope {
+  gf_ctx* ctx;
+  hipStream_t saved;
+  StreamScope(gf_ctx* c, hipStream_t s) : ctx(c), saved(c->stream) { c->stream = s; }
+  ~StreamScope() { ctx->stream = saved; }
+  StreamScope(const StreamScope&) = delete;
+  StreamScope& operator=(const StreamScope&) = delete;
+};
+
 inline bool grid_ok(const gf_grid* g) {
   return g && g->n > 0 && std::isfinite(g->minX) && std::isfinite(g->minY) && std::isfinite(g->cellLength) &&
          g->cellLength > 0.0;

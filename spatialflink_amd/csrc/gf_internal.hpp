@@ -683,7 +683,7 @@ hipError_t launch_knn_poly_sample(gf_ctx* ctx, const KnnPolyArgs& a);
 hipError_t launch_knn_poly_scan(gf_ctx* ctx, const KnnPolyArgs& a, int blocks);  // prefilter + refine
 struct KnnSelectArgs;
 struct KnnMergeArgs;
-// depth 2: prefilter of this window + (block 0) the previous window's select / window merge, then refine
+// pipelined: prefilter of this window + (block 0) an earlier window's select / window merge, then refine
 hipError_t launch_knn_poly_fused(gf_ctx* ctx, const KnnPolyArgs& a, const KnnSelectArgs& prev, int has_prev,
                                  int blocks, const KnnMergeArgs* merge);
 // k > kMaxK: the merge ranks every entry by binary searches in the other (sorted) records and
@@ -740,6 +740,8 @@ hipError_t launch_knn_fused(gf_ctx* ctx, const KnnScanArgs& a, const KnnSelectAr
 // gf_knn_enqueue with an optional window merge for the fused launch; *merged = 1 if it was
 // folded in (depth 2, a pending select, k <= kFusedMergeMaxK), else the caller launches it
 int knn_enqueue_merge(gf_knn_plan* P, const gf_points* pts, void* result, const KnnMergeArgs* merge, int* merged);
+// a window's select has not run yet (its record completes with a later launch or the flush)
+bool knn_select_pending(const gf_knn_plan* P);
 
 hipError_t launch_range(gf_ctx* ctx, const RangeArgs& a, int table_mode, int poly, int blocks);
 // a batch of windows of one plan in one launch (blockIdx.y = window; inline tests, DEFER 0)
@@ -996,27 +998,28 @@ struct gf_knn_plan {
   int32_t k = 0;
   int metric = 0;
   gf::QueryRect qr{};
-  // a lane = device state + candidate buffers of one in-flight window.  Lane 1 exists only
-  // at pipeline depth 2 (gf_knn_plan_set_pipeline): window i uses lane i % 2, and its select
-  // runs inside window i+1's fused scan kernel (or at gf_knn_plan_flush).
+  // A lane = device state (threshold, hint, counters) + candidate buffers of one window in
+  // flight.  Depth 1 uses lane 0.  Depth d >= 2 runs on S = d - 1 streams with two lanes each
+  // (gf_knn_plan_set_pipeline allocates lanes 1 .. 2S - 1): the window with sequence number q scans
+  // lane q % 2S on stream q % S, and its select runs in block 0 of window q + S's fused launch, on
+  // the same stream, or at gf_knn_plan_flush.  The unfused k in (kFusedSelectMaxK, kMaxK] uses
+  // lanes 0 .. S - 1, one per stream; the sorted path (large) lane 0 only.
   struct Lane {
     gf::KnnState* st = nullptr;
     double* cand_d = nullptr;
     uint32_t* cand_i = nullptr;
     int64_t* cand_o = nullptr;
-  } lane[6];  // depth d >= 3 uses 2 (d - 1): two per stream
+  } lane[6];  // 2S at depth 4
   int64_t cap = 0;
-  int pipeline = 1;               // 1: sample -> scan -> select per window; 2: fused
-  uint64_t seq = 0;
-  int pend_lane = -1;             // depth 2: the window whose select has not run yet
+  int pipeline = 1;               // depth: 1 sample -> scan -> select per window; 2 .. 4 fused launches
+  uint64_t seq = 0;               // depth >= 2: the next window's sequence number (0 after a depth change)
   int lane_warm[6] = {0, 0, 0, 0, 0, 0};  // depth >= 2: the lane has a hint from an earlier window
-  void* pend_result = nullptr;
-  int64_t pend_idx_base = 0;      // depth 2: idx_base of the pending window (set at its enqueue)
-  // depth 3: windows whose select has not run yet (seq k-1, k-2), oldest first
+  // depth >= 2: the windows whose select has not run yet (at most S), oldest first -- the one
+  // pending mechanism of every depth
   struct Pend {
     int lane;
     void* result;
-    int64_t idx_base;
+    int64_t idx_base;             // the index base in force when the window was enqueued
     uint64_t seq;
   };
   Pend pq[3];
@@ -1029,7 +1032,8 @@ struct gf_knn_plan {
   int scan_unroll = 2;   // x tiles (point pairs per lane) per iteration (tools/tune_fused.py sweep)
   int scan_nt = 1;       // nontemporal loads
   int large = 0;         // k > kMaxK: every candidate within r, sorted (knn_large)
-  // polygon query (gf_knn_ppoly_plan_create): device copy of the polygon, depth 1 only
+  // polygon query (gf_knn_ppoly_plan_create), every depth: device copy of the polygon and the
+  // prefilter scan's survivor buffers
   int poly = 0, approx = 0;
   int32_t* ring_off = nullptr;
   int32_t* vert_off = nullptr;
@@ -1037,7 +1041,7 @@ struct gf_knn_plan {
   double* vy = nullptr;
   double* ring_env = nullptr;
   double bbox[4] = {0, 0, 0, 0};
-  uint32_t* maybe_i[3] = {nullptr, nullptr, nullptr};  // per stream, cap entries
+  uint32_t* maybe_i[3] = {nullptr, nullptr, nullptr};  // one per stream (lane j uses j % S), cap entries
   int64_t maybe_cap = 0;
 };
 

@@ -199,22 +199,31 @@ __device__ __forceinline__ dbl2 ld2(const dbl2* p) {
   return *p;
 }
 
-__device__ __forceinline__ void wave_append(bool c, double d, uint32_t idx, const KnnScanArgs& a) {
+// Wave-aggregated reservation: the lanes with c set take consecutive slots of *ctr through one
+// atomicAdd by the first of them, and each of them calls store(its slot); what is stored, and any
+// capacity check, is the caller's.  Call it wave-uniformly.  The slot goes to a callable, not back
+// to the caller: returned, the compiler joins the empty-ballot path with the storing one and every
+// scan kernel's code changes; this shape compiles to what the hand-written copies did.
+template <class C, class Store>
+__device__ __forceinline__ void wave_reserve(C* ctr, bool c, Store&& store) {
   const uint64_t m = __ballot(c);
   if (m == 0) return;
   const int lane = threadIdx.x & 63;
   const int leader = __ffsll((unsigned long long)m) - 1;
-  unsigned long long base = 0;
-  if (lane == leader) base = atomicAdd(&a.st->count, (unsigned long long)__popcll(m));
+  C base = 0;
+  if (lane == leader) base = atomicAdd(ctr, (C)__popcll(m));
   base = __shfl(base, leader, 64);
-  if (c) {
-    const unsigned long long pos = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+  if (c) store(base + (C)__popcll(m & ((1ull << lane) - 1ull)));
+}
+
+__device__ __forceinline__ void wave_append(bool c, double d, uint32_t idx, const KnnScanArgs& a) {
+  wave_reserve(&a.st->count, c, [&](unsigned long long pos) {
     if (pos < a.cap) {
       a.cand_d[pos] = d;
       a.cand_i[pos] = idx;
       a.cand_o[pos] = a.objID[idx];
     }
-  }
+  });
 }
 
 // Per-iteration body shared by the unchecked main loop and the checked tail.
@@ -566,17 +575,7 @@ __device__ int dedupe_topk(LDS& L, int cnt, int k) {
 // wave-aggregated append into the LDS sort area
 template <class LDS>
 __device__ __forceinline__ void lds_push(LDS& L, bool c, uint64_t d, uint64_t o, int64_t i) {
-  const uint64_t m = __ballot(c);
-  if (m == 0) return;
-  const int lane = threadIdx.x & 63;
-  const int leader = __ffsll((unsigned long long)m) - 1;
-  int base = 0;
-  if (lane == leader) base = atomicAdd(&L.s_cnt, __popcll(m));
-  base = __shfl(base, leader, 64);
-  if (c) {
-    const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-    L.sd[pos] = d; L.so[pos] = o; L.si[pos] = i;
-  }
+  wave_reserve(&L.s_cnt, c, [&](int pos) { L.sd[pos] = d; L.so[pos] = o; L.si[pos] = i; });
 }
 
 // The bin of L.hist holding the target-th entry (1-based): L.s_bin, L.s_S = base + entries in
@@ -905,13 +904,7 @@ __global__ __launch_bounds__(kBlock) void knn_large_first_kernel(KnnLargeArgs a)
       p = a.perm[j];
       first = j == 0 || a.co[p] != a.co[a.perm[j - 1]];
     }
-    const uint64_t bal = __ballot(first);
-    if (bal == 0ull) continue;
-    const int leader = __ffsll((unsigned long long)bal) - 1;
-    uint32_t base = 0u;
-    if (lane == leader) base = atomicAdd(&a.cnt[1], (uint32_t)__popcll(bal));
-    base = __shfl(base, leader, 64);
-    if (first) a.out[base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = p;
+    wave_reserve(&a.cnt[1], first, [&](uint32_t pos) { a.out[pos] = p; });
   }
 }
 
@@ -1177,24 +1170,31 @@ __global__ __launch_bounds__(kMergeAnyT) void knn_merge_any_list_kernel(int32_t 
   knn_merge_any_body(k, src, nrec, result, scratch, 0);
 }
 
-// Fused continuous-query kernel (pipeline depth 2): blocks 1.. scan window i with the
-// threshold taken from the lane's hint (set by window i-2's select) -- or, for a lane's first
-// window (use_state 2), from the sample kernel launched just before; block 0, dispatched
-// first, runs window i-1's select on the other lane while they stream.  One launch per window.
-// Sliding windows: with m.nrec > 0, block 0 then merges the window that closed with window i-1
-// (its pane records, the one just written included) into m.result -- no separate merge launch.
+// Block 0 of a fused launch, point or polygon: the select of the window that ran S launches
+// earlier on this stream (has_prev) and, for a sliding window that closed with it (m.nrec > 0,
+// S = 1 only), the merge of its pane records -- the one just written included -- into m.result.
+__device__ __forceinline__ void fused_block0(const KnnSelectArgs& prev, int has_prev, const KnnMergeArgs& m,
+                                             SelLite& L) {
+  if (has_prev) knn_select_body<SelLite, false>(prev, L);
+  if (m.nrec > 0) {
+    __threadfence();  // the select's record stores, before the block reads them back
+    __syncthreads();
+    const ListRecs src{&m.list};
+    knn_merge_body(prev.k, src, m.nrec, m.result, L);
+  }
+}
+
+// Fused pipelined kernel (depth d >= 2, S = d - 1 streams): blocks 1.. scan window i with the
+// threshold taken from the lane's hint (set by window i - 2S's select) -- or, for a lane's first
+// window (use_state 2), from the sample kernel launched just before; block 0, dispatched first,
+// runs fused_block0 for window i - S on that window's lane while they stream.  One launch per
+// window, no separate select or merge launch.
 template <int METRIC, int U, int NT>
 __global__ __launch_bounds__(kBlock) void knn_fused_kernel(KnnScanArgs a, KnnSelectArgs prev, int has_prev,
                                                            KnnMergeArgs m) {
   __shared__ SelLite L;
   if (blockIdx.x == 0) {
-    if (has_prev) knn_select_body<SelLite, false>(prev, L);
-    if (m.nrec > 0) {
-      __threadfence();  // the select's record stores, before the block reads them back
-      __syncthreads();
-      const ListRecs src{&m.list};
-      knn_merge_body(prev.k, src, m.nrec, m.result, L);
-    }
+    fused_block0(prev, has_prev, m, L);
     return;
   }
   double T, sp;
@@ -1325,17 +1325,9 @@ __device__ __forceinline__ bool poly_maybe(const KnnPolyArgs& a, double px, doub
 }
 
 __device__ __forceinline__ void maybe_append(const KnnPolyArgs& a, bool c, int64_t i) {
-  const uint64_t m = __ballot(c);
-  if (m == 0) return;
-  const int lane = threadIdx.x & 63;
-  const int leader = __ffsll((unsigned long long)m) - 1;
-  unsigned long long base = 0;
-  if (lane == leader) base = atomicAdd(&a.st->maybe, (unsigned long long)__popcll(m));
-  base = __shfl(base, leader, 64);
-  if (c) {
-    const unsigned long long pos = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+  wave_reserve(&a.st->maybe, c, [&](unsigned long long pos) {
     if (pos < a.cap) a.maybe_i[pos] = (uint32_t)i;
-  }
+  });
 }
 
 // Two points per lane per iteration from 16-B loads of x and y (begin is even, x / y 16-B
@@ -1367,22 +1359,15 @@ __global__ __launch_bounds__(kBlock) void knn_poly_scan_kernel(KnnPolyArgs a) {
   knn_poly_scan_body(a, a.use_state ? a.st->T : a.r, blockIdx.x, gridDim.x);
 }
 
-// Polygon query at pipeline depth 2: blocks 1.. run window i's prefilter scan with the lane's
-// hint threshold (use_state 2: the sample just taken), block 0 the select of window i-1 (whose
-// refine ran before this launch) on the other lane -- and, for a sliding window closing with it,
-// the window merge.  Window i's refine follows in its own launch; its select rides in window
-// i+1's launch (or gf_knn_plan_flush).  Two launches per window instead of three.
+// Polygon query, pipelined: blocks 1.. run window i's prefilter scan with the lane's hint
+// threshold (use_state 2: the sample just taken), block 0 runs fused_block0 for window i - S,
+// whose refine ran before this launch.  Window i's refine follows in its own launch; its select
+// rides in window i + S's launch (or gf_knn_plan_flush).  Two launches per window instead of three.
 __global__ __launch_bounds__(kBlock) void knn_poly_fused_kernel(KnnPolyArgs a, KnnSelectArgs prev, int has_prev,
                                                                 KnnMergeArgs m) {
   __shared__ SelLite L;
   if (blockIdx.x == 0) {
-    if (has_prev) knn_select_body<SelLite, false>(prev, L);
-    if (m.nrec > 0) {
-      __threadfence();
-      __syncthreads();
-      const ListRecs src{&m.list};
-      knn_merge_body(prev.k, src, m.nrec, m.result, L);
-    }
+    fused_block0(prev, has_prev, m, L);
     return;
   }
   double T;
@@ -1417,20 +1402,13 @@ __global__ __launch_bounds__(kBlock) void knn_poly_refine_kernel(KnnPolyArgs a) 
       d = a.approx ? point_bbox_distance(px, py, a.bbox) : polygon_distance(px, py, a.poly, 0);
       c = d <= T;
     }
-    const uint64_t m = __ballot(c);
-    if (m == 0) continue;
-    const int leader = __ffsll((unsigned long long)m) - 1;
-    unsigned long long base = 0;
-    if (lane == leader) base = atomicAdd(&a.st->count, (unsigned long long)__popcll(m));
-    base = __shfl(base, leader, 64);
-    if (c) {
-      const unsigned long long pos = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+    wave_reserve(&a.st->count, c, [&a, d, i](unsigned long long pos) {
       if (pos < a.cap) {
         a.cand_d[pos] = d;
         a.cand_i[pos] = (uint32_t)i;
         a.cand_o[pos] = a.objID[i];
       }
-    }
+    });
   }
 }
 

@@ -191,14 +191,11 @@ extern "C" int gf_knn_plan_set_index_base(gf_knn_plan* P, int64_t base) {
   return GF_OK;
 }
 
-static int scan_blocks_for(gf_knn_plan* P, int64_t n) {
-  int blocks = P->scan_blocks;
-  if (blocks <= 0) {  // 4 blocks per CU: re-measured best for the x-first loop at 2 tiles per iteration
-    blocks = stream_blocks(P->ctx, (n + 1) / 2);
-    blocks = std::min(blocks, P->ctx->num_cus * 4);
-  }
-  return blocks;
-}
+// streams a plan's windows run on: S = depth - 1 once pipelined (depth 2: the context stream alone)
+static int knn_streams(const gf_knn_plan* P) { return P->pipeline >= 2 ? P->pipeline - 1 : 1; }
+
+// stream s of them: 0 = the context stream, then the extra ones
+static hipStream_t knn_stream(gf_ctx* ctx, int s) { return s == 0 ? ctx->stream : (s == 1 ? ctx->aux : ctx->aux2); }
 
 static KnnScanArgs scan_args(gf_knn_plan* P, int j, const gf_points* pts, int64_t begin, int64_t end, int use_state) {
   const gf_knn_plan::Lane& L = P->lane[j];
@@ -232,12 +229,16 @@ static KnnPolyArgs poly_args(gf_knn_plan* P, int j, const gf_points* pts, int64_
   for (int i = 0; i < 4; ++i) a.bbox[i] = P->bbox[i];
   a.approx = P->approx; a.r = P->r; a.k = P->k; a.use_state = use_state; a.use_hint = use_hint;
   a.st = L.st; a.cand_d = L.cand_d; a.cand_i = L.cand_i; a.cand_o = L.cand_o; a.cap = (unsigned long long)P->cap;
-  // one survivor buffer per stream (depth d >= 3: lane j runs on stream j % (d - 1); depth 2: lane j)
-  a.maybe_i = P->maybe_i[P->pipeline >= 3 ? j % (P->pipeline - 1) : j];
+  // One survivor buffer per stream: on every path lane j runs on stream j % S (the window with
+  // sequence number q uses lane q % 2S, or q % S unfused, on stream q % S; depth 1 and the sorted
+  // path use lane 0 on the context stream).  Lanes of one stream may share it -- at depth 2 both
+  // do -- because a window's scan, its refine and the next window's scan are stream-ordered: the
+  // buffer is consumed before it is written again, and its fill count st->maybe is per lane.
+  a.maybe_i = P->maybe_i[j % knn_streams(P)];
   return a;
 }
 
-// the polygon scan's prefilter-survivor buffers (cap entries per lane)
+// the polygon scan's prefilter-survivor buffers (cap entries per stream)
 static int poly_buffers(gf_knn_plan* P) {
   if (P->maybe_cap >= P->cap) return GF_OK;
   GF_HIP_CHECK(P->ctx, hipStreamSynchronize(P->ctx->stream));
@@ -251,21 +252,73 @@ static int poly_buffers(gf_knn_plan* P) {
   return GF_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// Point / polygon dispatch: the launches of one window on lane j, on the current ctx->stream.
+// Only these (and plan creation / destruction) look at P->poly.
+// ---------------------------------------------------------------------------------------
+// grid of a scan over n points: 4 blocks per CU at most (re-measured best for the x-first loop at
+// 2 tiles per iteration); the polygon prefilter runs on half the blocks a point scan of n would
+static int scan_blocks_for(gf_knn_plan* P, int64_t n) {
+  if (P->scan_blocks > 0) return P->scan_blocks;
+  const int64_t pairs = ((P->poly ? (n + 1) / 2 : n) + 1) / 2;
+  return std::min(stream_blocks(P->ctx, pairs), P->ctx->num_cus * 4);
+}
+
+// the window's threshold into the lane's state: its hint (use_hint, when it has one) or a sample
+static int launch_sample(gf_knn_plan* P, int j, const gf_points* pts, int use_hint) {
+  if (P->poly) {
+    GF_HIP_CHECK(P->ctx, launch_knn_poly_sample(P->ctx, poly_args(P, j, pts, 0, pts->n, 1, use_hint)));
+    return GF_OK;
+  }
+  KnnSampleArgs s{};
+  s.x = pts->x; s.y = pts->y; s.n = pts->n; s.qx = P->qx; s.qy = P->qy; s.qr = P->qr;
+  s.r = P->r; s.s_r = s_prefilter(P->r, P->metric); s.k = P->k; s.metric = P->metric; s.st = P->lane[j].st;
+  s.use_hint = use_hint;
+  GF_HIP_CHECK(P->ctx, launch_knn_sample(P->ctx, s));
+  return GF_OK;
+}
+
+// candidates of points [begin, end) into the lane (polygon: prefilter scan + refine)
+static int launch_scan(gf_knn_plan* P, int j, const gf_points* pts, int64_t begin, int64_t end, int use_state) {
+  gf_ctx* ctx = P->ctx;
+  const int blocks = scan_blocks_for(P, end - begin);
+  if (P->poly) {
+    if (int st = poly_buffers(P)) return st;
+    GF_HIP_CHECK(ctx, launch_knn_poly_scan(ctx, poly_args(P, j, pts, begin, end, use_state, 0), blocks));
+  } else {
+    GF_HIP_CHECK(ctx, launch_knn_scan(ctx, scan_args(P, j, pts, begin, end, use_state), blocks, P->scan_unroll,
+                                      P->scan_nt));
+  }
+  return GF_OK;
+}
+
+// the fused launch: the window's scan on lane j (use_state 2: the sample just taken, 1: the
+// lane's hint) and, in block 0, the select `prev` (has_prev) and the window merge (nullable);
+// polygon: the fused launch is the prefilter scan, the window's refine follows
+static int launch_fused(gf_knn_plan* P, int j, const gf_points* pts, int use_state, const KnnSelectArgs& prev,
+                        int has_prev, const KnnMergeArgs* merge) {
+  gf_ctx* ctx = P->ctx;
+  const int blocks = scan_blocks_for(P, pts->n);
+  if (P->poly) {
+    if (int st = poly_buffers(P)) return st;
+    GF_HIP_CHECK(ctx, launch_knn_poly_fused(ctx, poly_args(P, j, pts, 0, pts->n, use_state, 0), prev, has_prev, blocks,
+                                           merge));
+  } else {
+    GF_HIP_CHECK(ctx, launch_knn_fused(ctx, scan_args(P, j, pts, 0, pts->n, use_state), prev, has_prev, blocks,
+                                       P->scan_unroll, P->scan_nt, merge));
+  }
+  return GF_OK;
+}
+
+// a flagged window's first retry is the sample path with the hint ignored -- point queries only; a
+// polygon window goes straight to the exact sorted path
+static bool fallback_resamples(const gf_knn_plan* P) { return !P->poly; }
+
 // scan + select of points [begin, end) on lane j, stream-ordered
 static int knn_scan_select(gf_knn_plan* P, int j, const gf_points* pts, int64_t begin, int64_t end, int use_state,
                            int write_hint, void* result) {
-  gf_ctx* ctx = P->ctx;
-  if (P->poly) {
-    int st = poly_buffers(P);
-    if (st) return st;
-    const KnnPolyArgs a = poly_args(P, j, pts, begin, end, use_state, 0);
-    GF_HIP_CHECK(ctx, launch_knn_poly_scan(ctx, a, scan_blocks_for(P, (end - begin + 1) / 2)));
-    GF_HIP_CHECK(ctx, launch_knn_select(ctx, select_args(P, j, use_state, write_hint, result, P->idx_base)));
-    return GF_OK;
-  }
-  const KnnScanArgs s = scan_args(P, j, pts, begin, end, use_state);
-  GF_HIP_CHECK(ctx, launch_knn_scan(ctx, s, scan_blocks_for(P, end - begin), P->scan_unroll, P->scan_nt));
-  GF_HIP_CHECK(ctx, launch_knn_select(ctx, select_args(P, j, use_state, write_hint, result, P->idx_base)));
+  if (int st = launch_scan(P, j, pts, begin, end, use_state)) return st;
+  GF_HIP_CHECK(P->ctx, launch_knn_select(P->ctx, select_args(P, j, use_state, write_hint, result, P->idx_base)));
   return GF_OK;
 }
 
@@ -280,13 +333,7 @@ static int knn_large(gf_knn_plan* P, const gf_points* pts, void* result) {
   int st;
   const int64_t n = pts->n;
   if (P->cap < n && (st = knn_alloc_candidates(P, n))) return st;
-  if (P->poly) {  // JTS point-polygon distances (prefilter + refine), T = r
-    if ((st = poly_buffers(P))) return st;
-    GF_HIP_CHECK(ctx, launch_knn_poly_scan(ctx, poly_args(P, 0, pts, 0, n, 0, 0), scan_blocks_for(P, (n + 1) / 2)));
-  } else {
-    const KnnScanArgs s = scan_args(P, 0, pts, 0, n, 0);  // T = r
-    GF_HIP_CHECK(ctx, launch_knn_scan(ctx, s, scan_blocks_for(P, n), P->scan_unroll, P->scan_nt));
-  }
+  if ((st = launch_scan(P, 0, pts, 0, n, 0))) return st;  // T = r
   const gf_knn_plan::Lane& L = P->lane[0];
   const int64_t mm = std::max<int64_t>(n, 1);
   const int nb = radix_blocks(ctx, mm);
@@ -336,24 +383,6 @@ static int knn_large(gf_knn_plan* P, const gf_points* pts, void* result) {
   return GF_OK;
 }
 
-// stream s of a pipelined plan's windows in flight: 0 = the context stream, then the extra ones
-static hipStream_t knn_stream(gf_ctx* ctx, hipStream_t main, int s) {
-  return s == 0 ? main : (s == 1 ? ctx->aux : ctx->aux2);
-}
-
-static int knn_launch_sample(gf_knn_plan* P, int j, const gf_points* pts, int use_hint) {
-  if (P->poly) {
-    GF_HIP_CHECK(P->ctx, launch_knn_poly_sample(P->ctx, poly_args(P, j, pts, 0, pts->n, 1, use_hint)));
-    return GF_OK;
-  }
-  KnnSampleArgs s{};
-  s.x = pts->x; s.y = pts->y; s.n = pts->n; s.qx = P->qx; s.qy = P->qy; s.qr = P->qr;
-  s.r = P->r; s.s_r = s_prefilter(P->r, P->metric); s.k = P->k; s.metric = P->metric; s.st = P->lane[j].st;
-  s.use_hint = use_hint;
-  GF_HIP_CHECK(P->ctx, launch_knn_sample(P->ctx, s));
-  return GF_OK;
-}
-
 extern "C" int gf_knn_enqueue(gf_knn_plan* P, const gf_points* pts, void* result) {
   int merged = 0;
   return gf::knn_enqueue_merge(P, pts, result, nullptr, &merged);
@@ -371,124 +400,73 @@ int gf::knn_enqueue_merge(gf_knn_plan* P, const gf_points* pts, void* result, co
   // k > kMaxK: the sorted path queues without host reads at every depth (its record is complete
   // in stream order, earlier than a pipelined plan promises)
   if (P->large) return knn_large(P, pts, result);
-  if (P->pipeline >= 2 && P->k > kFusedSelectMaxK) {
+  if (P->pipeline == 1) {
+    // threshold: the previous window's hint (continuous query) or the sample; tiny windows
+    // scan to r
+    const bool staged = pts->n >= kSampleMinN;
+    if (staged && (st = launch_sample(P, 0, pts, P->use_hint))) return st;
+    return knn_scan_select(P, 0, pts, 0, pts->n, staged ? 1 : 0, staged && P->use_hint, result);
+  }
+  // Depth d >= 2, S = d - 1 streams (depth 2: the context stream alone).  The window with
+  // sequence number q runs on stream q % S; window buffers must be complete when enqueued (no
+  // cross-stream wait is inserted).
+  const uint64_t S = (uint64_t)knn_streams(P), q = P->seq++;
+  StreamScope on(ctx, knn_stream(ctx, (int)(q % S)));
+  if (P->k > kFusedSelectMaxK) {
     // k in (256, 512]: the select needs the standalone kernel's sort area, so it is not fused;
-    // each window runs [sample] + scan + select on its lane, complete in stream order (earlier
-    // than the depth promises).  Depth d >= 3 spreads windows over d - 1 streams with one lane
-    // each: a lane's hint chain stays on one stream and consecutive windows' kernels overlap.
-    const uint64_t kseq = P->seq++;
-    const int S = P->pipeline >= 3 ? P->pipeline - 1 : 1, j = (int)(kseq % (uint64_t)S);
-    hipStream_t main = ctx->stream;
-    ctx->stream = knn_stream(ctx, main, j);
+    // each window runs [sample] + scan + select on lane q % S, complete in stream order (earlier
+    // than the depth promises).  A lane's hint chain stays on one stream and, at S > 1,
+    // consecutive windows' kernels overlap.
+    const int j = (int)(q % S);
     const bool staged = pts->n >= kSampleMinN;  // the sample kernel takes the lane's hint when it has one
-    int rc = staged ? knn_launch_sample(P, j, pts, P->use_hint) : GF_OK;
-    if (rc == GF_OK) rc = knn_scan_select(P, j, pts, 0, pts->n, staged ? 1 : 0, staged && P->use_hint, result);
-    ctx->stream = main;
-    return rc;
+    if (staged && (st = launch_sample(P, j, pts, P->use_hint))) return st;
+    return knn_scan_select(P, j, pts, 0, pts->n, staged ? 1 : 0, staged && P->use_hint, result);
   }
-  if (P->pipeline >= 3) {
-    // depth d >= 3, S = d - 1 streams: window k launches on stream k % S, scans lane k % 2S and
-    // selects window k - S -- the previous launch on the SAME stream -- in block 0.  Every
-    // dependency (window k - S's candidates, lane k % 2S's last select in launch k - 2S, its hint)
-    // stays stream-ordered; consecutive windows' launches overlap (one's ramp-up under the
-    // other's tail), S of them in flight.  Polygon queries: the fused launch is the prefilter
-    // scan, the window's refine follows on the same stream (PointPolygonKNNQuery.java:245-317 per
-    // window).  Window buffers must be complete when enqueued (no cross-stream wait is inserted).
-    if (P->poly && (st = poly_buffers(P))) return st;
-    const uint64_t S = (uint64_t)(P->pipeline - 1), kseq = P->seq++;
-    const int j = (int)(kseq % (2 * S));
-    hipStream_t main = ctx->stream;
-    ctx->stream = knn_stream(ctx, main, (int)(kseq % S));
-    int rc = GF_OK;
-    do {
-      const bool sample = pts->n >= kSampleMinN && (!P->use_hint || !P->lane_warm[j]);
-      if (sample && (rc = knn_launch_sample(P, j, pts, 0))) break;
-      P->lane_warm[j] = 1;
-      KnnSelectArgs q{};
-      int has_prev = 0;
-      if (P->npq > 0 && P->pq[0].seq + S == kseq) {
-        const gf_knn_plan::Pend e = P->pq[0];
-        q = select_args(P, e.lane, 1, P->use_hint, e.result, e.idx_base);
-        has_prev = 1;
-        for (int t = 1; t < P->npq; ++t) P->pq[t - 1] = P->pq[t];
-        --P->npq;
-      }
-      hipError_t he;
-      if (P->poly)
-        he = launch_knn_poly_fused(ctx, poly_args(P, j, pts, 0, pts->n, sample ? 2 : 1, 0), q, has_prev,
-                                   scan_blocks_for(P, (pts->n + 1) / 2), nullptr);
-      else
-        he = launch_knn_fused(ctx, scan_args(P, j, pts, 0, pts->n, sample ? 2 : 1), q, has_prev,
-                              scan_blocks_for(P, pts->n), P->scan_unroll, P->scan_nt, merge);
-      if (he != hipSuccess) { rc = hip_err(ctx, he, "launch_knn_fused"); break; }
-      P->pq[P->npq++] = gf_knn_plan::Pend{j, result, P->idx_base, kseq};
-    } while (0);
-    ctx->stream = main;
-    return rc;
+  // One fused launch per window: it scans lane q % 2S (threshold = the lane's hint) and selects
+  // window q - S -- the previous launch on the SAME stream -- in block 0; this window's select
+  // rides the launch of window q + S, or the flush.  Every dependency (window q - S's
+  // candidates, the lane's last select in launch q - 2S, its hint) stays stream-ordered, while
+  // S consecutive windows' launches overlap (one's ramp-up under the other's tail).
+  const int j = (int)(q % (2 * S));
+  // a lane's first window (or hints off): sample the threshold instead of guessing r
+  const bool sample = pts->n >= kSampleMinN && (!P->use_hint || !P->lane_warm[j]);
+  if (sample && (st = launch_sample(P, j, pts, 0))) return st;
+  P->lane_warm[j] = 1;
+  KnnSelectArgs prev{};
+  int has_prev = 0;
+  if (P->npq > 0 && P->pq[0].seq + S == q) {
+    const gf_knn_plan::Pend e = P->pq[0];
+    prev = select_args(P, e.lane, 1, P->use_hint, e.result, e.idx_base);
+    has_prev = 1;
+    std::copy(P->pq + 1, P->pq + P->npq, P->pq);
+    --P->npq;
   }
-  if (P->pipeline == 2) {
-    // one fused launch: scan this window on lane j (threshold = the lane's hint), select the
-    // pending previous window on the other lane in block 0; this window's select rides the next
-    // launch.  Polygon query: the fused launch is the prefilter scan, then this window's refine
-    const int j = (int)(P->seq++ & 1);
-    if (P->poly && (st = poly_buffers(P))) return st;
-    // a lane's first window (or hints off): sample the threshold instead of guessing r
-    const bool sample = pts->n >= kSampleMinN && (!P->use_hint || !P->lane_warm[j]);
-    if (sample && (st = knn_launch_sample(P, j, pts, 0))) return st;
-    P->lane_warm[j] = 1;
-    const int use_state = sample ? 2 : 1;
-    KnnSelectArgs q{};
-    const int has_prev = P->pend_lane >= 0;
-    if (has_prev) q = select_args(P, P->pend_lane, 1, P->use_hint, P->pend_result, P->pend_idx_base);
-    const bool fold = merge && merge->nrec > 0 && has_prev && P->k <= kFusedMergeMaxK;
-    if (P->poly)
-      GF_HIP_CHECK(ctx, launch_knn_poly_fused(ctx, poly_args(P, j, pts, 0, pts->n, use_state, 0), q, has_prev,
-                                             scan_blocks_for(P, (pts->n + 1) / 2), fold ? merge : nullptr));
-    else
-      GF_HIP_CHECK(ctx, launch_knn_fused(ctx, scan_args(P, j, pts, 0, pts->n, use_state), q, has_prev,
-                                         scan_blocks_for(P, pts->n), P->scan_unroll, P->scan_nt,
-                                         fold ? merge : nullptr));
-    *merged = fold ? 1 : 0;
-    P->pend_lane = j;
-    P->pend_result = result;
-    P->pend_idx_base = P->idx_base;  // the index base in force when this window was enqueued
-    return GF_OK;
-  }
-  // threshold: the previous window's hint (continuous query) or the sample; tiny windows
-  // scan to r
-  const bool staged = pts->n >= kSampleMinN;
-  if (staged && (st = knn_launch_sample(P, 0, pts, P->use_hint))) return st;
-  return knn_scan_select(P, 0, pts, 0, pts->n, staged ? 1 : 0, staged && P->use_hint, result);
+  // the pane engine's window merge rides block 0 too where its select does (depth 2 only)
+  const bool fold = S == 1 && merge && merge->nrec > 0 && has_prev && P->k <= kFusedMergeMaxK;
+  if ((st = launch_fused(P, j, pts, sample ? 2 : 1, prev, has_prev, fold ? merge : nullptr))) return st;
+  *merged = fold ? 1 : 0;
+  P->pq[P->npq++] = gf_knn_plan::Pend{j, result, P->idx_base, q};  // the index base in force at this enqueue
+  return GF_OK;
 }
+
+bool gf::knn_select_pending(const gf_knn_plan* P) { return P->npq > 0; }
 
 extern "C" int gf_knn_plan_flush(gf_knn_plan* P) {
   if (!P) return GF_ERR_ARG;
-  if (P->pipeline >= 3) {
-    if (P->npq == 0) return P->k > kFusedSelectMaxK ? gf_ctx_join(P->ctx) : GF_OK;  // mid k: the other streams
-    gf_ctx* ctx = P->ctx;
-    int st = bind(ctx);
-    if (st) return st;
-    hipStream_t main = ctx->stream;
-    for (int e = 0; e < P->npq; ++e) {
-      const gf_knn_plan::Pend& w = P->pq[e];
-      ctx->stream = knn_stream(ctx, main, (int)(w.seq % (uint64_t)(P->pipeline - 1)));
-      hipError_t he = launch_knn_select(ctx, select_args(P, w.lane, 1, P->use_hint, w.result, w.idx_base));
-      ctx->stream = main;
-      if (he != hipSuccess) return hip_err(ctx, he, "launch_knn_select");
-    }
-    P->npq = 0;
-    // every window of the plan is complete in the context stream's order from here on
-    return gf_ctx_join(ctx);
-  }
-  if (P->pend_lane < 0) return GF_OK;
   gf_ctx* ctx = P->ctx;
+  const int S = knn_streams(P);
+  // nothing pending: only the unfused mid-range k at S > 1 has put work on the other streams
+  if (P->npq == 0) return S > 1 && P->k > kFusedSelectMaxK ? gf_ctx_join(ctx) : GF_OK;
   int st = bind(ctx);
   if (st) return st;
-  GF_HIP_CHECK(ctx, launch_knn_select(ctx, select_args(P, P->pend_lane, 1, P->use_hint, P->pend_result,
-                                                       P->pend_idx_base)));
-  P->pend_lane = -1;
-  P->pend_result = nullptr;
-  return GF_OK;
+  for (int e = 0; e < P->npq; ++e) {
+    const gf_knn_plan::Pend& w = P->pq[e];
+    StreamScope on(ctx, knn_stream(ctx, (int)(w.seq % (uint64_t)S)));
+    GF_HIP_CHECK(ctx, launch_knn_select(ctx, select_args(P, w.lane, 1, P->use_hint, w.result, w.idx_base)));
+  }
+  P->npq = 0;
+  // every window of the plan is complete in the context stream's order from here on
+  return S > 1 ? gf_ctx_join(ctx) : GF_OK;
 }
 
 extern "C" int gf_knn_plan_set_pipeline(gf_knn_plan* P, int depth) {
@@ -500,7 +478,7 @@ extern "C" int gf_knn_plan_set_pipeline(gf_knn_plan* P, int depth) {
   if (int e = sync_aux(ctx)) return e;
   // k > 512 plans return through knn_large (lane 0, stream-ordered) before any pipelined path:
   // no extra lanes, no second stream
-  const int lanes = depth >= 3 ? 2 * (depth - 1) : depth;
+  const int lanes = depth >= 2 ? 2 * (depth - 1) : 1;
   for (int j = 1; !P->large && j < lanes; ++j)
     if (!P->lane[j].st && (st = knn_alloc_lane(P, j, P->cap))) return st;
   if (depth >= 3 && !P->large && !ctx->aux)
@@ -510,7 +488,6 @@ extern "C" int gf_knn_plan_set_pipeline(gf_knn_plan* P, int depth) {
   P->pipeline = depth;
   P->seq = 0;
   for (int& w : P->lane_warm) w = 0;
-  P->npq = 0;
   return GF_OK;
 }
 
@@ -575,8 +552,8 @@ static int knn_fallback(gf_knn_plan* P, const gf_points* pts, int64_t* oo, doubl
   };
   int st = gf_knn_plan_flush(P);  // lane 0 is free afterwards
   if (st) return st;
-  if (!P->poly && pts->n >= kSampleMinN) {
-    if ((st = knn_launch_sample(P, 0, pts, 0)) ||
+  if (fallback_resamples(P) && pts->n >= kSampleMinN) {
+    if ((st = launch_sample(P, 0, pts, 0)) ||
         (st = knn_scan_select(P, 0, pts, 0, pts->n, 1, P->use_hint, P->tmp_result)) || (st = fetch()))
       return st;
     if (h->status == 0) return gf_knn_decode(P, pts, P->host_result, oo, od, oi, n_out);

@@ -180,7 +180,7 @@ extern "C" int gf_knn_sliding_push(gf_knn_sliding* s, int64_t pane_index, const 
     if (!window_result) return set_err(ctx, GF_ERR_ARG, "gf_knn_sliding_push: a window closes, result is null");
     *closed = 1;
     if (window_end) *window_end = (pane_index + 1) * s->pane_ms;
-    if (P->pend_lane >= 0) {
+    if (knn_select_pending(P)) {
       s->pend = true;
       s->pend_last = pane_index;
       s->pend_result = window_result;
