@@ -64,7 +64,8 @@ extern "C" {
 #define GF_K_TSTATS      13 /* trajectories: tStats */
 #define GF_K_TRAJ_SELECT 14 /* trajectories: sub-trajectory extraction */
 #define GF_K_TAGG        15 /* tAggregate: its own kernels (the grouping kernels count as GF_K_TRAJ_GROUP, the radix passes as GF_K_BUCKET) */
-#define GF_K_COUNT       16
+#define GF_K_TKNN        16 /* tKnn: its own kernels (the grouping kernels count as GF_K_TRAJ_GROUP, the radix passes as GF_K_BUCKET) */
+#define GF_K_COUNT       17
 
 typedef struct gf_ctx gf_ctx;
 
@@ -731,6 +732,69 @@ int  gf_tagg_read_all(gf_tagg* t, int64_t* off, int64_t* keys, int64_t* len, int
 int  gf_tagg_rows(const char* function, int64_t cells, const int64_t* count, const int64_t* multi, const int64_t* sum,
                   const int64_t* minLen, const int64_t* minKey, const int64_t* maxLen, const int64_t* maxKey,
                   uint8_t* emit, int64_t* value, int64_t* key, int32_t* kind);
+
+/* ---- tKnn: the window-based trajectory kNN ---------------------------------------------------
+ * tKnn/PointPointTKNNQuery.java windowBased (GF_TKNN_GRID, `run`) and windowBasedNaive (GF_TKNN_NAIVE,
+ * `runNaive`) with TKNNQuery.java:50-101 kNNEvaluationWindowed, for one device-resident window of
+ * n < 2^32 points already grouped by objID (gf_traj_group): the k trajectories nearest to the query
+ * point (qx, qy).  Flink's emission orders are unspecified and the reference depends on them in three
+ * places; this contract fixes each by first-occurrence order, never by scheduling.
+ *  1. Cells.  A point's cell is K1's (cx, cy) (HelperClass.assignGridCellID, Java (int) saturation,
+ *     NaN -> 0).  The cell set N:
+ *       GRID, r != 0:  L = getCandidateNeighboringLayers(r); L <= 0 -> GF_ERR_LAYERS (as the join);
+ *                      N = the cells with |cx - qcx| <= L, |cy - qcy| <= L and validKey
+ *                      (UniformGrid.java:261-293), tested arithmetically per point
+ *       GRID, r == 0:  N = every valid cell (girdCellsSet)
+ *       NAIVE:         N = every cell a point falls in, cells outside the grid included; the key is
+ *                      the int32 pair as for tAggregate, with its caveat about the String key
+ *     Quirk kept: the window mode never compares a distance with r.
+ *  2. Distance.  d_i = sqrt((qy - y_i) * (qy - y_i) + (qx - x_i) * (qx - x_i)), the sum in that order
+ *     (DistanceFunctions.java:60-63), binary64 without FMA.  GF_METRIC_* does not apply: tKnn never
+ *     goes through JTS.  A NaN distance is reported as Double.doubleToLongBits' NaN, 0x7ff8000000000000.
+ *  3. Per (cell c in N, objID o), over o's points in c in window order (TKNNQuery.java:72-83: the first
+ *     sets the value, a later one replaces it iff new < cur):  d(c, o) = NaN iff the first such point's
+ *     distance is NaN, else the minimum of the non-NaN distances.
+ *  4. Per cell the list L_c: its k smallest pairs by (d under Double.compareTo -- NaN last --, then
+ *     the trajectory's rank t).  t = the trajectory's first-occurrence rank in the whole window
+ *     (gf_traj_group's order); Java's tie order is HashMap iteration order.  The rank, not the key, on
+ *     purpose: it does not depend on dictionary ids.
+ *  5. Per trajectory t in at least one list: cells_t = the number of lists holding it, D_t = the least
+ *     d(c, t) over THOSE lists under compareTo (NAIVE takes this minimum, :586-588; GRID takes the
+ *     first record to arrive, :259-262, of which the least is the one legal outcome independent of
+ *     arrival).  Not o's minimum over N: the truncation of step 4 happens first, and is observable.
+ *  6. Size rule.  t is dropped unless it has >= 2 points in the WHOLE window (points outside N and
+ *     outside the grid count: the join is against the unfiltered stream; the reference's
+ *     coordinateList.size() > 1 with size = cells_t x len_t).
+ *  7. Result: the k smallest survivors by (D_t under compareTo, t).  Per row: key, D_t, cells_t and the
+ *     whole trajectory (x, y, ts, idx = window index, in arrival order) as CSR in result order.  The
+ *     reference's LineString repeats the trajectory's points cells_t times (a join artefact); each point
+ *     is emitted once here and cells_t reported.  Any int64 is a legal key.  Results are identical
+ *     from run to run.
+ *  8. k < 1, a NaN query coordinate, a NaN or negative r, an unknown mode, a null groups object / grid
+ *     / pts / x / y / objID / ts, or pts that is not the grouped window: GF_ERR_ARG before any device
+ *     call.  An empty N or an empty window: no rows, GF_OK.
+ * Not covered: the RealTime paths, CountBased, sliding panes, sharding across GPUs, JNI bindings, the
+ * non-point tKnn pairs.
+ *
+ * gf_tknn_run: *out == NULL: a new object; otherwise that object (of the groups' context) is reused with
+ * its device workspace.  Sync.  gf_tknn_info: rows, their points, and what the window reached:
+ * in_cells = points in N, pairs = distinct (cell, objID) pairs, records = the sum of |L_c|. */
+#define GF_TKNN_GRID  0
+#define GF_TKNN_NAIVE 1
+typedef struct gf_tknn gf_tknn;
+int  gf_tknn_run(gf_traj_groups* g, const gf_grid* grid, const gf_points* pts, double qx, double qy, double r,
+                 int32_t k, int mode, gf_tknn** out);
+void gf_tknn_destroy(gf_tknn* t);
+int  gf_tknn_info(const gf_tknn* t, int64_t* rows, int64_t* npts, int64_t* in_cells, int64_t* pairs, int64_t* records);
+/* The rows into HOST arrays (any may be NULL): at most cap_rows keys / dist / cells and
+ * off[0 .. min(rows, cap_rows)], at most cap_pts points; the full counts are gf_tknn_info's.  Sync. */
+int  gf_tknn_read(gf_tknn* t, int64_t* keys, double* dist, int32_t* cells, int64_t* off, int64_t cap_rows, double* x,
+                  double* y, int64_t* ts, uint32_t* idx, int64_t cap_pts);
+/* Testing / tuning: cells of at least big_cell pairs are ranked by one sort of all pairs, smaller ones
+ * by counting inside the cell (>= 1; 0 = the default, 512).  Takes effect at the next gf_tknn_run;
+ * results are identical for any value.  (The pair minima are order-free atomics for every pair, however
+ * many points it holds: there is no long-pair path and so no threshold for one.) */
+int  gf_tknn_set_thresholds(gf_tknn* t, int64_t big_cell);
 
 /* ---- pinned host memory ---------------------------------------------------------------
  * Mapped, portable host memory: kernels write kNN records straight into it (pass it as the

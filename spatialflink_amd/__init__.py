@@ -4,7 +4,8 @@ The Java operators' per-window bodies (range, kNN, join) run as hand-written HIP
 for gfx950 behind the C ABI in include/geoflink_hip.h; this package is the host-side
 mirror of the reference operator API (UniformGrid, Point, Polygon, QueryConfiguration,
 PointPointRangeQuery, PointPolygonRangeQuery, PointPointKNNQuery, PointPointJoinQuery,
-PointPolygonKNNQuery, PointPolygonJoinQuery, PointTStatsQuery).
+PointPolygonKNNQuery, PointPolygonJoinQuery, PointTStatsQuery, PointTAggregateQuery,
+PointPointTKNNQuery).
 """
 from . import _lib, sharding
 from .spatialIndices import UniformGrid, generateCellIDStr, getIntCellIndices, padLeadingZeroesToInt
@@ -13,6 +14,7 @@ from .spatialOperators import (KNNResult, PinnedRecords, PointPointJoinQuery, Po
                                PointPolygonJoinQuery, PointPolygonKNNQuery, PointTStatsQuery, SubTrajectories,
                                TrajectoryGroups, TStatsResult, group_by_objid, sub_trajectories,
                                PointTAggregateQuery, TAggregateGroups, TAggregateResult, tagg_rows,
+                               PointPointTKNNQuery, TKNNResult,
                                PointPolygonRangeQuery, QueryConfiguration, QueryType, RangeResult, assign_cells,
                                bucket_by_cell, knn_merge_host, synthetic_uniform,
                                synthetic_clustered)
@@ -20,6 +22,7 @@ from .spatialStreams import Deserialization
 from .windows import SlidingKNNQuery, SlidingRangeQuery, SlidingWindows
 
 __all__ = [
+    "PointPointTKNNQuery", "TKNNResult",
     "PointTAggregateQuery", "TAggregateResult", "TAggregateGroups", "tagg_rows",
     "PointTStatsQuery", "TStatsResult", "SubTrajectories", "TrajectoryGroups", "group_by_objid", "sub_trajectories",
     "SlidingWindows", "SlidingKNNQuery", "SlidingRangeQuery", "Deserialization", "PointPolygonKNNQuery", "PointPolygonJoinQuery",

@@ -30,6 +30,8 @@ GF_COMM_ID_BYTES = 128
 
 METRIC_SQRT = 0
 METRIC_HYPOT = 1
+TKNN_GRID = 0   # gf_tknn_run modes: PointPointTKNNQuery.run
+TKNN_NAIVE = 1  # .runNaive
 
 FLAG_JOIN_LEGACY = 1
 FLAG_JOIN_COARSE = 2
@@ -38,7 +40,7 @@ FLAG_GEOJSON_WAVE = 16
 FLAG_GEOJSON_CHECK = 32
 FLAG_JOIN_STREAM = 8
 (K_KNN_SCAN, K_KNN_SAMPLE, K_KNN_SELECT, K_RANGE_SCAN, K_ASSIGN, K_JOIN_PROBE, K_RANGE_TEST, K_JOIN_BUCKET,
- K_KNN_MERGE, K_CSV_PARSE, K_BUCKET, K_JOIN_COMPACT, K_TRAJ_GROUP, K_TSTATS, K_TRAJ_SELECT, K_TAGG) = range(16)
+ K_KNN_MERGE, K_CSV_PARSE, K_BUCKET, K_JOIN_COMPACT, K_TRAJ_GROUP, K_TSTATS, K_TRAJ_SELECT, K_TAGG, K_TKNN) = range(17)
 
 # Every symbol include/geoflink_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = [
@@ -69,6 +71,7 @@ EXPORTS = [
     "gf_traj_groups_set_long_threshold", "gf_tstats_run", "gf_traj_select",
     "gf_tagg_group", "gf_tagg_run", "gf_tagg_destroy", "gf_tagg_info", "gf_tagg_set_thresholds", "gf_tagg_read_cells",
     "gf_tagg_read_all", "gf_tagg_rows",
+    "gf_tknn_run", "gf_tknn_destroy", "gf_tknn_info", "gf_tknn_read", "gf_tknn_set_thresholds",
 ]
 
 
@@ -253,6 +256,12 @@ def lib():
             "gf_tagg_read_cells": ([P, P, P, P, P, P, P, P, P, P, i64, pi64], C.c_int),
             "gf_tagg_read_all": ([P, P, P, P, i64, i64, pi64, pi64], C.c_int),
             "gf_tagg_rows": ([C.c_char_p, i64, P, P, P, P, P, P, P, P, P, P, pi32], C.c_int),
+            "gf_tknn_run": ([P, C.POINTER(GfGrid), C.POINTER(GfPoints), C.c_double, C.c_double, C.c_double, C.c_int32,
+                             C.c_int, C.POINTER(P)], C.c_int),
+            "gf_tknn_destroy": ([P], None),
+            "gf_tknn_info": ([P, pi64, pi64, pi64, pi64, pi64], C.c_int),
+            "gf_tknn_read": ([P, P, P, P, P, i64, P, P, P, P, i64], C.c_int),
+            "gf_tknn_set_thresholds": ([P, i64], C.c_int),
         }
         for name, (argt, rest) in sig.items():
             if os.environ.get("GF_LIB_PATH") and not hasattr(L, name):

@@ -56,3 +56,17 @@ int group_dense_ids(gf_ctx* ctx, KeyGroups& K, const int64_t* key, int64_t n, co
 int group_sort_ids(gf_ctx* ctx, KeyGroups& K, const uint32_t* ids, int64_t n, uint32_t nids);
 
 }  // namespace gf
+
+// a window grouped by objID (gf_traj_group, traj.cpp): trajectory t = dense id t; tknn.cpp reads did,
+// perm, seg_off and keys
+struct gf_traj_groups : gf::KeyGroups {
+  gf_ctx* ctx = nullptr;
+  int64_t ntraj = 0;
+  int64_t long_len = gf::kTrajLongLen;
+  // tStats
+  gf::DevBuf S, T, V, long_list, counters, set, sel, srank, ck, cS, cT, cV;
+  // sub-trajectories
+  gf::DevBuf hit, len, row, off, okeys, ooff, ox, oy, ots, oidx;
+  gf::DevBuf* all[23] = {&S, &T, &V, &long_list, &counters, &set, &sel, &srank, &ck, &cS, &cT, &cV, &hit, &len,
+                     &row, &off, &okeys, &ooff, &ox, &oy, &ots, &oidx, nullptr};
+};

@@ -649,6 +649,75 @@ struct TaggArgs {
 // stage 0: cell keys; 1: composite keys; 2: per-group statistics; 3: per-cell aggregation + ALL rows
 hipError_t launch_tagg(gf_ctx* ctx, int stage, const TaggArgs& a);
 
+// tKnn (k_tknn.hip, tknn.cpp)
+constexpr int64_t kTknnBigCell = 512;  // default: cells of at least this many (cell, objID) pairs are ranked by the sort
+constexpr unsigned long long kTknnNaN = 0x7FF8000000000000ull;  // Double.doubleToLongBits(NaN): above +inf as an integer
+constexpr unsigned long long kTknnNone = ~0ull;                 // no distance yet (above every distance)
+struct TknnArgs {
+  // scan (stage 0): the window's one pass
+  const double* x;
+  const double* y;
+  const uint32_t* did;      // [n] trajectory (dense objID id) per point
+  int64_t n;
+  double minX, minY, cl, qx, qy;
+  int32_t xlo, xhi, ylo, yhi;  // N = the cells of this rectangle (inclusive), unless
+  int32_t naive;            // every cell is in N
+  int64_t* e_ckey;          // entries (the points in N, in no particular order): pack(cx, cy),
+  uint32_t* e_t;            //   the trajectory,
+  unsigned long long* e_d;  //   the distance's bits (NaN = kTknnNaN),
+  uint32_t* e_i;            //   the window index
+  uint32_t* counters;       // zero before stage 0: [0] entries, [1] pairs of big cells, [2] records
+  // entries (stages 1, 2)
+  int64_t m;
+  const uint32_t* cid;      // [m] dense cell id per entry
+  int64_t* comp;            // [m] cid << 32 | trajectory
+  const uint32_t* pid;      // [m] dense pair id per entry
+  // pairs (stages 2 .. 5)
+  int64_t npairs;
+  const int64_t* pkeys;     // [npairs] the pairs' composite keys
+  uint32_t* p_first;        // [npairs] smallest window index of the pair
+  unsigned long long* p_d;  // [npairs] d(c, o) as bits
+  uint32_t* p_cell;         // [npairs] dense cell id
+  uint32_t* p_rec;          // [npairs] 1: the pair is in its cell's list L_c
+  const uint32_t* gperm;    // pairs sorted stably by cell id; cell c = gperm[cell_off[c], cell_off[c + 1])
+  const uint32_t* gcell;    // [npairs] the cell id per gperm position
+  const uint32_t* cell_off;
+  const uint32_t* sperm;    // pairs sorted by (cell id, d, trajectory) (big cells)
+  uint32_t big_cell;
+  int32_t k;
+  // trajectories (stages 5, 6)
+  int64_t ntraj;
+  const uint32_t* seg_off;  // gf_traj_groups' segments: the size rule
+  unsigned long long* tr_D; // [ntraj] D_t as bits (kTknnNone: in no list)
+  uint32_t* tr_cells;       // [ntraj] cells_t
+  uint32_t* surv;           // [ntraj] survivor flags
+  const uint32_t* srank;    // [ntraj + 1] their scan
+  uint32_t* slist;          // [survivors] the surviving trajectories, ascending
+  // result (stages 7, 8)
+  int64_t rows, npts;
+  const uint32_t* order;    // [survivors] survivor ranks by (D_t, t)
+  const int64_t* tkeys;     // [ntraj] objID keys
+  const uint32_t* perm;     // gf_traj_groups' perm
+  const int64_t* ts;
+  int64_t* o_key;
+  double* o_dist;
+  int32_t* o_cells;
+  uint32_t* o_traj;         // [rows] the row's trajectory
+  uint32_t* o_len;          // [rows]
+  const uint32_t* o_off;    // [rows + 1] scan of o_len
+  double* o_x;
+  double* o_y;
+  int64_t* o_ts;
+  uint32_t* o_idx;
+};
+// stage 0 scan; 1 compose; 2 pair minima; 3 small cells' lists; 4 big cells' lists; 5 combine per
+// trajectory + survivor flags; 6 survivor list; 7 rows; 8 gather
+hipError_t launch_tknn(gf_ctx* ctx, int stage, const TknnArgs& a);
+// out[p] = (uint32)(src[index ? index[item] : item] >> shift), item = cur ? cur[p] : p: one 32-bit
+// word of a multi-word sort key, in the current order
+hipError_t launch_tknn_word(gf_ctx* ctx, const unsigned long long* src, const uint32_t* index, int shift,
+                            const uint32_t* cur, int64_t cnt, uint32_t* out);
+
 hipError_t launch_knn_sample(gf_ctx* ctx, const KnnSampleArgs& a);
 hipError_t launch_knn_scan(gf_ctx* ctx, const KnnScanArgs& a, int blocks, int unroll, int nt);
 hipError_t launch_knn_select(gf_ctx* ctx, const KnnSelectArgs& a);

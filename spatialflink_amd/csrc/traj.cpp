@@ -17,18 +17,6 @@
 
 using namespace gf;
 
-struct gf_traj_groups : KeyGroups {
-  gf_ctx* ctx = nullptr;
-  int64_t ntraj = 0;
-  int64_t long_len = kTrajLongLen;
-  // tStats
-  DevBuf S, T, V, long_list, counters, set, sel, srank, ck, cS, cT, cV;
-  // sub-trajectories
-  DevBuf hit, len, row, off, okeys, ooff, ox, oy, ots, oidx;
-  DevBuf* all[23] = {&S, &T, &V, &long_list, &counters, &set, &sel, &srank, &ck, &cS, &cT, &cV, &hit, &len,
-                     &row, &off, &okeys, &ooff, &ox, &oy, &ots, &oidx, nullptr};
-};
-
 static int scan_u32(gf_traj_groups* G, const uint32_t* in, int64_t L, uint32_t* out) {
   return group_scan_u32(G->ctx, *G, in, L, out);
 }

@@ -735,7 +735,40 @@ class TrajectoryGroups:
         k, q = m.value, npts.value
         return SubTrajectories(self.window, keys[:k], off[:k + 1], x[:q], y[:q], ts[:q], idx[:q])
 
+    def tknn(self, grid: UniformGrid, queryPoint, queryRadius: float, k: int, naive: bool = False, big_cell=None,
+             cap_rows=None, cap_pts=None) -> "TKNNResult":
+        """gf_tknn_run over this grouped window (PointPointTKNNQuery.run / runNaive without grouping the
+        window again).  The gf_tknn object is kept and reused by later calls.  big_cell: the testing
+        threshold of gf_tknn_set_thresholds (0: the default); cap_rows / cap_pts: read at most that many
+        rows / points (default: all).  The result carries `info`: rows, npts, in_cells, pairs, records."""
+        if getattr(self, "_tknn", None) is None:
+            self._tknn = C.c_void_p()
+        L = _lib.lib()
+        if big_cell is not None and not self._tknn:
+            raise ValueError("big_cell needs an earlier tknn() call on these groups")
+        if big_cell is not None:
+            _lib.check(L.gf_tknn_set_thresholds(self._tknn, int(big_cell)), None, "gf_tknn_set_thresholds")
+        pts = self.window.c_struct()
+        st = L.gf_tknn_run(self.handle, C.byref(grid.c_grid), C.byref(pts), float(queryPoint.x), float(queryPoint.y),
+                           float(queryRadius), int(k), _lib.TKNN_NAIVE if naive else _lib.TKNN_GRID, C.byref(self._tknn))
+        _lib.check(st, self.ctx.handle, "gf_tknn_run")
+        c = [C.c_int64() for _ in range(5)]
+        _lib.check(L.gf_tknn_info(self._tknn, *(C.byref(v) for v in c)), None, "gf_tknn_info")
+        info = dict(zip(("rows", "npts", "in_cells", "pairs", "records"), (v.value for v in c)))
+        m = info["rows"] if cap_rows is None else min(info["rows"], int(cap_rows))
+        q = info["npts"] if cap_pts is None else min(info["npts"], int(cap_pts))
+        keys, dist, cells, off = np.empty(m, np.int64), np.empty(m, np.float64), np.empty(m, np.int32), np.zeros(m + 1, np.int64)
+        x, y, ts, idx = np.empty(q, np.float64), np.empty(q, np.float64), np.empty(q, np.int64), np.empty(q, np.uint32)
+        st = L.gf_tknn_read(self._tknn, keys.ctypes.data, dist.ctypes.data, cells.ctypes.data, off.ctypes.data, m,
+                            x.ctypes.data, y.ctypes.data, ts.ctypes.data, idx.ctypes.data, q)
+        _lib.check(st, self.ctx.handle, "gf_tknn_read")
+        return TKNNResult(self.window, keys, dist, cells, off, x, y, ts, idx, info)
+
     def close(self):
+        t = getattr(self, "_tknn", None)
+        if t and _lib._lib is not None:
+            _lib._lib.gf_tknn_destroy(t)
+            self._tknn = None
         h = getattr(self, "handle", None)
         if h and _lib._lib is not None:
             _lib._lib.gf_traj_groups_destroy(h)
@@ -1027,7 +1060,80 @@ class PointTAggregateQuery:
                                 off, keys, lens, window.start, window.end)
 
 
+# ----------------------------------------------------------------------------------------
+# tKnn (the window-based trajectory kNN)
+# ----------------------------------------------------------------------------------------
+@dataclass
+class TKNNResult:
+    """The rows of the window-based tKnn, nearest first: objID (keys), dist = D_t, cells = cells_t and
+    the whole trajectory of row j as points [off[j], off[j + 1]) of x, y, ts, idx (idx = index in the
+    window) in arrival order.  The contract is include/geoflink_hip.h's."""
+
+    window: PointWindow
+    objID: np.ndarray
+    dist: np.ndarray
+    cells: np.ndarray
+    off: np.ndarray
+    x: np.ndarray
+    y: np.ndarray
+    ts: np.ndarray
+    idx: np.ndarray
+    info: dict = None
+
+    def __len__(self):
+        return len(self.objID)
+
+    def objid_strings(self):
+        """The rows' objID Strings, through the window's dictionary."""
+        return self.window.objid_strings(self.objID)
+
+    def tuples(self):
+        """(objID String, distance) per row."""
+        return list(zip(self.objid_strings(), self.dist.tolist()))
+
+    def linestrings(self, repeat: bool = False):
+        """The rows' coordinate lists [(x, y), ...]; repeat=True: each list repeated cells times, the
+        reference's LineString (its join emits the trajectory once per cell list holding it)."""
+        off, xs, ys = self.off.tolist(), self.x.tolist(), self.y.tolist()
+        out = []
+        for j in range(len(off) - 1):
+            ls = list(zip(xs[off[j]:off[j + 1]], ys[off[j]:off[j + 1]]))
+            out.append(ls * int(self.cells[j]) if repeat else ls)
+        return out
+
+
+class PointPointTKNNQuery:
+    """tKnn/PointPointTKNNQuery.java windowBased (run) and windowBasedNaive (runNaive) +
+    TKNNQuery.kNNEvaluationWindowed: the k trajectories nearest to a query point, each whole.  The
+    window mode never compares a distance with the radius (a quirk kept): the radius only selects the
+    cells.  WindowBased only; the RealTime and CountBased variants raise as unsupported."""
+
+    def __init__(self, conf: QueryConfiguration, index: UniformGrid = None):
+        self.conf = conf
+        self.index = index
+
+    def _run(self, window, queryPoint, queryRadius, k, naive, groups):
+        if self.conf.getQueryType() != QueryType.WindowBased:
+            raise ValueError("Not yet support")
+        if self.index is None:
+            raise ValueError("PointPointTKNNQuery needs the grid")
+        g = groups if groups is not None else TrajectoryGroups(window)
+        try:
+            return g.tknn(self.index, queryPoint, queryRadius, k, naive=naive)
+        finally:
+            if groups is None:
+                g.close()
+
+    def run(self, window: PointWindow, queryPoint: Point, queryRadius: float, k: int, groups=None) -> TKNNResult:
+        """groups: the window's TrajectoryGroups, if the caller has grouped it already."""
+        return self._run(window, queryPoint, queryRadius, k, False, groups)
+
+    def runNaive(self, window: PointWindow, queryPoint: Point, queryRadius: float, k: int, groups=None) -> TKNNResult:
+        return self._run(window, queryPoint, queryRadius, k, True, groups)
+
+
 __all__ = [
+    "PointPointTKNNQuery", "TKNNResult",
     "PointTAggregateQuery", "TAggregateResult", "TAggregateGroups", "tagg_rows",
     "PointTStatsQuery", "TStatsResult", "SubTrajectories", "TrajectoryGroups", "group_by_objid", "sub_trajectories",
     "synthetic_clustered", "QueryType", "QueryConfiguration", "PointPointRangeQuery", "PointPolygonRangeQuery", "PointPointKNNQuery",
