@@ -65,7 +65,8 @@ extern "C" {
 #define GF_K_TRAJ_SELECT 14 /* trajectories: sub-trajectory extraction */
 #define GF_K_TAGG        15 /* tAggregate: its own kernels (the grouping kernels count as GF_K_TRAJ_GROUP, the radix passes as GF_K_BUCKET) */
 #define GF_K_TKNN        16 /* tKnn: its own kernels (the grouping kernels count as GF_K_TRAJ_GROUP, the radix passes as GF_K_BUCKET) */
-#define GF_K_COUNT       17
+#define GF_K_TJOIN       17 /* tJoin: its own kernels (the radix passes count as GF_K_BUCKET) */
+#define GF_K_COUNT       18
 
 typedef struct gf_ctx gf_ctx;
 
@@ -795,6 +796,74 @@ int  gf_tknn_read(gf_tknn* t, int64_t* keys, double* dist, int32_t* cells, int64
  * results are identical for any value.  (The pair minima are order-free atomics for every pair, however
  * many points it holds: there is no long-pair path and so no threshold for one.) */
 int  gf_tknn_set_thresholds(gf_tknn* t, int64_t big_cell);
+
+/* ---- tJoin: the window-based trajectory join ---------------------------------------------------
+ * tJoin/PointPointTJoinQuery.java windowBased (GF_TJOIN_PAIR, `run`) and commonSingle (GF_TJOIN_SINGLE,
+ * `runSingle`, :341-435) with TJoinQuery.java, for one device-resident ordinary window O and one query
+ * window Q, each already grouped by objID (gf_traj_group), n_o, n_q < 2^32, timestamps >= 0 (as for
+ * tStats), one grid for both sides: the pairs of trajectories with a point of one within r of a point of
+ * the other, each pair once, each trajectory whole.
+ *  1. Matching point pairs: exactly the pair set of
+ *       gf_join_pp(ctx, grid, grid, O, Q, r, approximate = 0, GF_METRIC_SQRT, ...).
+ *     q is replicated to getNeighboringCells(r, q) (UniformGrid.java:261-293): the valid cells within
+ *     L = getCandidateNeighboringLayers(r) layers of q's cell (q itself may lie outside the grid); r == 0:
+ *     every valid cell.  L <= 0 -> GF_ERR_LAYERS.  p joins on its own cell, which must be a valid cell.  A
+ *     pair survives iff getPointPointEuclideanDistance(p, q) <= r, binary64 without FMA: the sum of the
+ *     two squares commutes, so the value is bit-identical to GF_METRIC_SQRT's.  NaN never matches.
+ *  2. Rows: the distinct (t_o, t_q) with at least one matching pair (p of t_o, q of t_q), t = the
+ *     trajectory's first-occurrence rank in its own window (gf_traj_group's order), ascending by
+ *     (t_o, t_q).  Flink's emission order is unspecified; this is the fixed one.
+ *  3. Row fields.  okey, qkey: the objID keys (any int64 is a legal key).
+ *     q_latest: the window index of the matching q of t_q with the largest ts, among equal ts the smallest
+ *       index -- the secondIDPointMap loop (PointPointTJoinQuery.java:263-281) replaces iff
+ *       new.ts > old.ts, so the first arrival wins a tie; arrival is fixed as the query window's order.
+ *     p_first: the smallest ordinary window index of t_o matching any point of t_q.  The reference's
+ *       firstPoint of an ordinary objID (the ordinary point of the first pair to arrive for it; arrival
+ *       fixed as the ordinary window's order) is the minimum of p_first over that objID's rows.
+ *  4. Size rule.  emit = (t_o has >= 2 points in the WHOLE of O) and (t_q has >= 2 in the whole of Q)
+ *     (GenerateWindowedTrajectory, TJoinQuery.java:184: the two joins against the trajectory streams drop
+ *     the rest; points outside the grid count).  Rows with emit = 0 stay in the row table -- they are
+ *     runSingle's Point-pair output -- and own no trajectory in the CSR.
+ *  5. Trajectories.  Per side the distinct trajectories of the emitted rows, ascending rank, each whole
+ *     and once, as CSR: keys[m], off[m + 1], x, y, ts, idx (window index) in arrival order.  An emitted
+ *     row carries oslot / qslot, its positions in those two lists (emit = 0: -1).  The reference emits a
+ *     Tuple2<LineString, LineString> per row; this is that without copying a trajectory per partner.
+ *  6. GF_TJOIN_SINGLE: one window against itself; go == gq (the same object) and rows of equal objID are
+ *     excluded.  Deviation: the reference writes `p.objID != q.objID` on Strings, a reference comparison
+ *     whose outcome depends on JVM object identity after serialisation; a C ABI cannot express that, and
+ *     the evident intent ("no need to join a trajectory with itself") is kept.
+ *  7. A NaN r, an unknown mode, a null object / grid / pts / x / y / objID / ts (either side), groups of
+ *     different contexts, pts that are not the grouped windows, SINGLE with two different groups objects:
+ *     GF_ERR_ARG before any device call.  An empty window on either side: no rows, GF_OK.  Results are
+ *     identical from run to run.
+ * Not covered: the RealTime paths and their triggers, realTimeJoinNaive, sliding panes, sharding across
+ * GPUs, JNI bindings.
+ *
+ * gf_tjoin_run: *out == NULL: a new object; otherwise that object (of the groups' context) is reused, its
+ * device workspace grow-only.  The rows are collected in a device hash table whose size is not known
+ * beforehand: it starts from the object's previous window (or a default), and when a probe finds it more
+ * than half full the library doubles it and probes again -- the caller sees no capacity error, only
+ * probe_passes; GF_ERR_NOMEM when the table would outgrow what min(n_o x n_q, free memory) allows.  Sync.
+ * gf_tjoin_info: rows, emitted rows, the CSRs' trajectories and points per side, probe runs of the last
+ * call. */
+#define GF_TJOIN_PAIR 0
+#define GF_TJOIN_SINGLE 1
+typedef struct gf_tjoin gf_tjoin;
+int  gf_tjoin_run(gf_traj_groups* go, const gf_points* opts, gf_traj_groups* gq, const gf_points* qpts,
+                  const gf_grid* grid, double r, int mode, gf_tjoin** out);
+void gf_tjoin_destroy(gf_tjoin* t);
+int  gf_tjoin_info(const gf_tjoin* t, int64_t* rows, int64_t* emitted, int64_t* otraj, int64_t* opoints,
+                   int64_t* qtraj, int64_t* qpoints, int64_t* probe_passes);
+/* The row table into HOST arrays (any may be NULL): at most cap rows; the full count is gf_tjoin_info's.  Sync. */
+int  gf_tjoin_read_rows(gf_tjoin* t, int64_t* okey, int64_t* qkey, uint32_t* p_first, uint32_t* q_latest,
+                        uint8_t* emit, int32_t* oslot, int32_t* qslot, int64_t cap);
+/* One side's CSR (0 ordinary, 1 query) into HOST arrays (any may be NULL): at most cap_traj keys and
+ * off[0 .. min(m, cap_traj)], at most cap_pts points.  Sync. */
+int  gf_tjoin_read_trajs(gf_tjoin* t, int side, int64_t* keys, int64_t* off, int64_t cap_traj,
+                         double* x, double* y, int64_t* ts, uint32_t* idx, int64_t cap_pts);
+/* Testing: the table's size at the next gf_tjoin_run (a power of two >= 16; 0 = the default).  Results are
+ * identical for any value. */
+int  gf_tjoin_set_table_slots(gf_tjoin* t, int64_t slots);
 
 /* ---- pinned host memory ---------------------------------------------------------------
  * Mapped, portable host memory: kernels write kNN records straight into it (pass it as the

@@ -5,7 +5,7 @@ for gfx950 behind the C ABI in include/geoflink_hip.h; this package is the host-
 mirror of the reference operator API (UniformGrid, Point, Polygon, QueryConfiguration,
 PointPointRangeQuery, PointPolygonRangeQuery, PointPointKNNQuery, PointPointJoinQuery,
 PointPolygonKNNQuery, PointPolygonJoinQuery, PointTStatsQuery, PointTAggregateQuery,
-PointPointTKNNQuery).
+PointPointTKNNQuery, PointPointTJoinQuery).
 """
 from . import _lib, sharding
 from .spatialIndices import UniformGrid, generateCellIDStr, getIntCellIndices, padLeadingZeroesToInt
@@ -14,7 +14,7 @@ from .spatialOperators import (KNNResult, PinnedRecords, PointPointJoinQuery, Po
                                PointPolygonJoinQuery, PointPolygonKNNQuery, PointTStatsQuery, SubTrajectories,
                                TrajectoryGroups, TStatsResult, group_by_objid, sub_trajectories,
                                PointTAggregateQuery, TAggregateGroups, TAggregateResult, tagg_rows,
-                               PointPointTKNNQuery, TKNNResult,
+                               PointPointTKNNQuery, TKNNResult, PointPointTJoinQuery, TJoinResult,
                                PointPolygonRangeQuery, QueryConfiguration, QueryType, RangeResult, assign_cells,
                                bucket_by_cell, knn_merge_host, synthetic_uniform,
                                synthetic_clustered)
@@ -22,6 +22,7 @@ from .spatialStreams import Deserialization
 from .windows import SlidingKNNQuery, SlidingRangeQuery, SlidingWindows
 
 __all__ = [
+    "PointPointTJoinQuery", "TJoinResult",
     "PointPointTKNNQuery", "TKNNResult",
     "PointTAggregateQuery", "TAggregateResult", "TAggregateGroups", "tagg_rows",
     "PointTStatsQuery", "TStatsResult", "SubTrajectories", "TrajectoryGroups", "group_by_objid", "sub_trajectories",

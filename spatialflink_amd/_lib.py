@@ -32,6 +32,8 @@ METRIC_SQRT = 0
 METRIC_HYPOT = 1
 TKNN_GRID = 0   # gf_tknn_run modes: PointPointTKNNQuery.run
 TKNN_NAIVE = 1  # .runNaive
+TJOIN_PAIR = 0    # gf_tjoin_run modes: PointPointTJoinQuery.run
+TJOIN_SINGLE = 1  # .runSingle
 
 FLAG_JOIN_LEGACY = 1
 FLAG_JOIN_COARSE = 2
@@ -40,7 +42,8 @@ FLAG_GEOJSON_WAVE = 16
 FLAG_GEOJSON_CHECK = 32
 FLAG_JOIN_STREAM = 8
 (K_KNN_SCAN, K_KNN_SAMPLE, K_KNN_SELECT, K_RANGE_SCAN, K_ASSIGN, K_JOIN_PROBE, K_RANGE_TEST, K_JOIN_BUCKET,
- K_KNN_MERGE, K_CSV_PARSE, K_BUCKET, K_JOIN_COMPACT, K_TRAJ_GROUP, K_TSTATS, K_TRAJ_SELECT, K_TAGG, K_TKNN) = range(17)
+ K_KNN_MERGE, K_CSV_PARSE, K_BUCKET, K_JOIN_COMPACT, K_TRAJ_GROUP, K_TSTATS, K_TRAJ_SELECT, K_TAGG, K_TKNN,
+ K_TJOIN) = range(18)
 
 # Every symbol include/geoflink_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = [
@@ -72,6 +75,8 @@ EXPORTS = [
     "gf_tagg_group", "gf_tagg_run", "gf_tagg_destroy", "gf_tagg_info", "gf_tagg_set_thresholds", "gf_tagg_read_cells",
     "gf_tagg_read_all", "gf_tagg_rows",
     "gf_tknn_run", "gf_tknn_destroy", "gf_tknn_info", "gf_tknn_read", "gf_tknn_set_thresholds",
+    "gf_tjoin_run", "gf_tjoin_destroy", "gf_tjoin_info", "gf_tjoin_read_rows", "gf_tjoin_read_trajs",
+    "gf_tjoin_set_table_slots",
 ]
 
 
@@ -262,6 +267,13 @@ def lib():
             "gf_tknn_info": ([P, pi64, pi64, pi64, pi64, pi64], C.c_int),
             "gf_tknn_read": ([P, P, P, P, P, i64, P, P, P, P, i64], C.c_int),
             "gf_tknn_set_thresholds": ([P, i64], C.c_int),
+            "gf_tjoin_run": ([P, C.POINTER(GfPoints), P, C.POINTER(GfPoints), C.POINTER(GfGrid), C.c_double, C.c_int,
+                              C.POINTER(P)], C.c_int),
+            "gf_tjoin_destroy": ([P], None),
+            "gf_tjoin_info": ([P, pi64, pi64, pi64, pi64, pi64, pi64, pi64], C.c_int),
+            "gf_tjoin_read_rows": ([P, P, P, P, P, P, P, P, i64], C.c_int),
+            "gf_tjoin_read_trajs": ([P, C.c_int, P, P, i64, P, P, P, P, i64], C.c_int),
+            "gf_tjoin_set_table_slots": ([P, i64], C.c_int),
         }
         for name, (argt, rest) in sig.items():
             if os.environ.get("GF_LIB_PATH") and not hasattr(L, name):

@@ -55,6 +55,20 @@ int group_dense_ids(gf_ctx* ctx, KeyGroups& K, const int64_t* key, int64_t n, co
 // ids (K.kbuf[K.sorted_in]) and K.seg_off[nids + 1].  Enqueued; ids may be K.did.
 int group_sort_ids(gf_ctx* ctx, KeyGroups& K, const uint32_t* ids, int64_t n, uint32_t nids);
 
+// One word of a multi-word key: item q's word = (uint32)(src[index ? index[q] : q] >> shift), `bits` wide.
+struct SortWord {
+  const unsigned long long* src;
+  const uint32_t* index;
+  int shift, bits;
+};
+// Stable LSD radix sort of the items [0, cnt) by the words given, least significant first: *out[p] =
+// the item at sorted position p (one of sp[0], sp[1]); `start` = the order to begin from (null: the
+// identity; not one of sp).  Every word is read in the order the words before it left (launch_tknn_word
+// into wkey), then sorted by digits of <= kRadixMaxBits bits as group_sort_ids does, in K's radix
+// workspace.  Enqueued.  tknn.cpp and tjoin.cpp share it.
+int group_sort_words(gf_ctx* ctx, KeyGroups& K, DevBuf& wkey, DevBuf sp[2], const SortWord* words, int nwords, int64_t cnt,
+                     const uint32_t* start, const uint32_t** out);
+
 }  // namespace gf
 
 // a window grouped by objID (gf_traj_group, traj.cpp): trajectory t = dense id t; tknn.cpp reads did,

@@ -718,6 +718,107 @@ hipError_t launch_tknn(gf_ctx* ctx, int stage, const TknnArgs& a);
 hipError_t launch_tknn_word(gf_ctx* ctx, const unsigned long long* src, const uint32_t* index, int shift,
                             const uint32_t* cur, int64_t cnt, uint32_t* out);
 
+// tJoin (k_tjoin.hip, tjoin.cpp)
+constexpr int64_t kTjoinSlots = 1 << 16;            // default: the least first table size
+constexpr int64_t kTjoinMinSlots = 16;
+constexpr unsigned long long kTjoinEmpty = ~0ull;   // no (t_o, t_q) packs to it: both ranks are < 2^32 - 1
+constexpr int kTjoinShardStride = 32;               // uint32 between two shard counters (128 B apart)
+constexpr uint32_t kTjoinMaxShards = 1024;
+// The row table: open addressing, linear probe.  Rows are counted per SHARD of home slots (a key's shard
+// is fixed by its hash, so whether a shard overflows depends on the key set alone, never on arrival):
+// shard_cap * shards = slots / 2.
+struct TjoinTable {
+  unsigned long long* key;  // [slots] t_o << 32 | t_q (kTjoinEmpty: free)
+  uint32_t* qrank;          // [slots] least qrank of a matching q (0xFFFFFFFF before the first)
+  uint32_t* pfirst;         // [slots] least matching ordinary index
+  uint64_t mask;            // slots - 1
+  uint32_t* count;          // [shards * kTjoinShardStride] rows claimed per shard
+  uint32_t shard_shift;     // shard = home slot >> shard_shift
+  uint32_t shard_cap;
+  uint32_t* overflow;       // set when a shard passes shard_cap (or a probe finds no free slot): the pass is void
+};
+struct TjoinArgs {
+  // query side
+  const double* qx;
+  const double* qy;
+  const int64_t* qts;
+  const uint32_t* qdid;     // [nq] trajectory per query point
+  const uint32_t* qseg;     // [ntq + 1] gq's seg_off
+  const uint32_t* qperm;    // gq's perm
+  const int64_t* qkeys;     // [ntq]
+  int64_t nq, ntq;
+  const uint32_t* bkey;     // [nq] clamped bucket key (launch_join_qkeys)
+  const int32_t* qcx;       // [nq] the real cells
+  const int32_t* qcy;
+  unsigned long long* its;  // [nq] ~ts: ascending = ts descending
+  unsigned long long* comp; // [nq] bucket key << 32 | trajectory
+  const uint32_t* ord;      // [nq] the query points by (trajectory, ts descending, index)
+  uint32_t* qrank;          // [nq] position among the trajectory's points in that order
+  uint32_t* qord;           // [nq] a copy of ord: qord[qseg[t] + qrank] = the window index
+  const uint32_t* sidx;     // [nq] the query points by (bucket, trajectory, qrank)
+  double2* sxy;             // [nq] bucket order: coordinates,
+  int4* smeta;              //   real cell x, y, trajectory, run_end,
+  uint32_t* sqr;            //   qrank
+  uint32_t* flag;           // [nq + 1] 1: first element of its (bucket, trajectory) run
+  const uint32_t* fscan;    // [nq + 1] exclusive scan of flag
+  uint32_t* rstart;         // [nq + 1] first position of run i; rstart[runs] = nq
+  uint32_t* boff;           // [nb + 1] first position of bucket b; boff[nb] = nq
+  int64_t nb;               // (qn + 2)^2
+  // ordinary side
+  const double* ox;
+  const double* oy;
+  const int64_t* ots;
+  const uint32_t* odid;
+  const uint32_t* oseg;
+  const uint32_t* operm;
+  const int64_t* okeys;
+  int64_t no, nto;
+  unsigned long long* ocell;  // [no] cy * qn + cx, or qn * qn outside the grid
+  const uint32_t* oord;     // [no] the ordinary points by that key (the probe's order)
+  double minX, minY, cl, r;
+  int32_t qn;
+  int64_t c;                // candidate layers; < 0: r == 0, every bucket
+  int32_t single;
+  TjoinTable t;
+  // rows
+  int64_t slots, rows;
+  uint32_t* occ;            // [slots + 1] 1: slot holds a row
+  const uint32_t* cpos;     // [slots + 1] its scan
+  unsigned long long* rkey; // [rows] the rows compacted in slot order
+  uint32_t* rqr;
+  uint32_t* rpf;
+  const uint32_t* rorder;   // [rows] compacted rows by (t_o, t_q)
+  int64_t* o_okey;          // [rows] the row table
+  int64_t* o_qkey;
+  uint32_t* o_pfirst;
+  uint32_t* o_qlatest;
+  uint8_t* o_emit;
+  int32_t* o_oslot;
+  int32_t* o_qslot;
+  uint32_t* o_to;           // [rows] the rows' ranks
+  uint32_t* o_tq;
+  uint32_t* mark[2];        // [nt + 1] per side: trajectory owns an emitted row
+  const uint32_t* mrank[2]; // [nt + 1] their scans
+  uint32_t* counters;       // [8] zero before the rows stage: [0] emitted rows; totals (stage 12): [1] ordinary
+                            // trajectories, [2] their points, [3] query trajectories, [4] their points
+  // CSR of one side (stages 11 .. 13)
+  int32_t side;
+  int64_t nt;               // the side's trajectories
+  uint32_t* tlist[2];       // [nt] emitted trajectories, ascending
+  uint32_t* tlen[2];        // [nt + 1] their lengths (zero past the last)
+  const uint32_t* toff[2];  // [nt + 1] scan of tlen
+  int64_t m, npts;          // the side's emitted trajectories and points
+  int64_t* c_keys;
+  double* c_x;
+  double* c_y;
+  int64_t* c_ts;
+  uint32_t* c_idx;
+};
+// stage 0 query keys; 1 qrank + qord; 2 bucket-order arrays + run flags; 3 run starts + bucket offsets;
+// 4 run ends; 5 ordinary cell keys; 6 probe; 7 occupied flags; 8 compact; 9 rows + marks; 10 slots;
+// 11 one side's trajectory list; 12 totals; 13 one side's gather
+hipError_t launch_tjoin(gf_ctx* ctx, int stage, const TjoinArgs& a);
+
 hipError_t launch_knn_sample(gf_ctx* ctx, const KnnSampleArgs& a);
 hipError_t launch_knn_scan(gf_ctx* ctx, const KnnScanArgs& a, int blocks, int unroll, int nt);
 hipError_t launch_knn_select(gf_ctx* ctx, const KnnSelectArgs& a);

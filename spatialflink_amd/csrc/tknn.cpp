@@ -1,8 +1,8 @@
 // tknn.cpp -- tKnn entry points of the C ABI (tKnn/PointPointTKNNQuery.java windowBased /
 // windowBasedNaive, TKNNQuery.java:50-101): gf_tknn_run over a window already grouped by objID
 // (gf_traj_group), the read and the testing hook.  The kernels are in k_tknn.hip; the groupings by
-// cell and by (cell, trajectory) and the sort of the pairs by cell are gf_group.hpp's (traj.cpp); the
-// multi-word sorts run k_points.hip's radix passes.  The object owns its device workspace (grow-only)
+// cell and by (cell, trajectory), the sort of the pairs by cell and the multi-word sorts are
+// gf_group.hpp's (traj.cpp), run on k_points.hip's radix passes.  The object owns its device workspace (grow-only)
 // and is reused across windows.
 #define GF_TU_NAME tknn_cpp
 #include "gf_buildtag.hpp"  // first: records this unit's command-line defines
@@ -42,60 +42,6 @@ static int key_bits(uint64_t nids) {
   int bits = 1;
   while (((uint64_t)1 << bits) < nids) ++bits;
   return bits;
-}
-
-// One word of a multi-word key: item q's word = (uint32)(src[index ? index[q] : q] >> shift), `bits` wide.
-struct SortWord {
-  const unsigned long long* src;
-  const uint32_t* index;
-  int shift, bits;
-};
-
-// Stable LSD radix sort of the items [0, cnt) by the words given, least significant first: *out[p] =
-// the item at sorted position p (one of T->sp).  Every word is read in the order the words before it
-// left (tknn_word), then sorted by digits of <= kRadixMaxBits bits as group_sort_ids does.
-static int sort_words(gf_tknn* T, const SortWord* words, int nwords, int64_t cnt, const uint32_t** out) {
-  gf_ctx* ctx = T->ctx;
-  KeyGroups& K = T->srt;
-  int st = GF_OK;
-  const size_t w = sizeof(uint32_t) * (size_t)(cnt + 1);
-  if ((st = K.kbuf[0].reserve(ctx, w)) || (st = K.kbuf[1].reserve(ctx, w)) || (st = K.vbuf[0].reserve(ctx, w)) ||
-      (st = K.vbuf[1].reserve(ctx, w)) || (st = T->wkey.reserve(ctx, w)) || (st = T->sp[0].reserve(ctx, w)) ||
-      (st = T->sp[1].reserve(ctx, w)))
-    return st;
-  const int blocks = radix_blocks(ctx, cnt);
-  const uint32_t* cur = nullptr;  // the current order (null: the identity)
-  int next = 0;
-  for (int iw = 0; iw < nwords; ++iw) {
-    const SortWord& W = words[iw];
-    const int passes = (W.bits + kRadixMaxBits - 1) / kRadixMaxBits, pbits = (W.bits + passes - 1) / passes;
-    const int64_t mat = ((int64_t)1 << pbits) * blocks;
-    if ((st = K.mat.reserve(ctx, sizeof(uint32_t) * (size_t)mat)) ||
-        (st = K.mats.reserve(ctx, sizeof(uint32_t) * (size_t)(mat + 1))))
-      return st;
-    GF_HIP_CHECK(ctx, launch_tknn_word(ctx, W.src, W.index, W.shift, cur, cnt, T->wkey.as<uint32_t>()));
-    RadixArgs r{};
-    r.tile = radix_tile();
-    r.n = cnt;
-    r.bits = pbits;
-    r.nblk = blocks;
-    r.M = K.mat.as<uint32_t>();
-    r.Ms = K.mats.as<uint32_t>();
-    for (int p = 0; p < passes; ++p) {
-      r.kin = p == 0 ? T->wkey.as<uint32_t>() : K.kbuf[(p - 1) & 1].as<uint32_t>();
-      r.vin = p == 0 ? cur : K.vbuf[(p - 1) & 1].as<uint32_t>();  // null: the index is the position
-      r.kout = K.kbuf[p & 1].as<uint32_t>();
-      r.vout = p == passes - 1 ? T->sp[next].as<uint32_t>() : K.vbuf[p & 1].as<uint32_t>();
-      r.shift = p * pbits;
-      GF_HIP_CHECK(ctx, launch_radix(ctx, 0, r, blocks));
-      if ((st = group_scan_u32(ctx, K, r.M, mat, K.mats.as<uint32_t>()))) return st;
-      GF_HIP_CHECK(ctx, launch_radix(ctx, 1, r, blocks));
-    }
-    cur = T->sp[next].as<uint32_t>();
-    next ^= 1;
-  }
-  *out = cur;
-  return GF_OK;
 }
 
 static int tknn_window(gf_tknn* T, gf_traj_groups* G, const gf_grid* grid, const gf_points* pts, double qx, double qy,
@@ -164,7 +110,7 @@ static int tknn_window(gf_tknn* T, gf_traj_groups* G, const gf_grid* grid, const
                                {a.p_d, nullptr, 0, 32},
                                {a.p_d, nullptr, 32, 32},
                                {pk, nullptr, 32, key_bits((uint64_t)ncells)}};
-    if ((st = sort_words(T, words, 4, npairs, &a.sperm))) return st;
+    if ((st = group_sort_words(ctx, T->srt, T->wkey, T->sp, words, 4, npairs, nullptr, &a.sperm))) return st;
     GF_HIP_CHECK(ctx, launch_tknn(ctx, 4, a));
   }
   // per trajectory: D_t, cells_t, the size rule
@@ -185,7 +131,7 @@ static int tknn_window(gf_tknn* T, gf_traj_groups* G, const gf_grid* grid, const
   if (nsurv == 0) return GF_OK;
   // the survivors (ascending t) sorted stably by D_t = by (D_t, t); the first k are the rows
   const SortWord dw[2] = {{a.tr_D, a.slist, 0, 32}, {a.tr_D, a.slist, 32, 32}};
-  if ((st = sort_words(T, dw, 2, nsurv, &a.order))) return st;
+  if ((st = group_sort_words(ctx, T->srt, T->wkey, T->sp, dw, 2, nsurv, nullptr, &a.order))) return st;
   const int64_t rows = std::min<int64_t>(nsurv, k);
   const size_t nr = (size_t)rows;
   if ((st = T->o_key.reserve(ctx, nr * 8)) || (st = T->o_dist.reserve(ctx, nr * 8)) || (st = T->o_cells.reserve(ctx, nr * 4)) ||

@@ -109,6 +109,49 @@ int gf::group_sort_ids(gf_ctx* ctx, KeyGroups& K, const uint32_t* ids, int64_t n
   return GF_OK;
 }
 
+int gf::group_sort_words(gf_ctx* ctx, KeyGroups& K, DevBuf& wkey, DevBuf sp[2], const SortWord* words, int nwords,
+                         int64_t cnt, const uint32_t* start, const uint32_t** out) {
+  int st = GF_OK;
+  const size_t w = sizeof(uint32_t) * (size_t)(cnt + 1);
+  if ((st = K.kbuf[0].reserve(ctx, w)) || (st = K.kbuf[1].reserve(ctx, w)) || (st = K.vbuf[0].reserve(ctx, w)) ||
+      (st = K.vbuf[1].reserve(ctx, w)) || (st = wkey.reserve(ctx, w)) || (st = sp[0].reserve(ctx, w)) ||
+      (st = sp[1].reserve(ctx, w)))
+    return st;
+  const int blocks = radix_blocks(ctx, cnt);
+  const uint32_t* cur = start;  // the current order (null: the identity)
+  int next = 0;
+  for (int iw = 0; iw < nwords; ++iw) {
+    const SortWord& W = words[iw];
+    const int passes = (W.bits + kRadixMaxBits - 1) / kRadixMaxBits, pbits = (W.bits + passes - 1) / passes;
+    const int64_t mat = ((int64_t)1 << pbits) * blocks;
+    if ((st = K.mat.reserve(ctx, sizeof(uint32_t) * (size_t)mat)) ||
+        (st = K.mats.reserve(ctx, sizeof(uint32_t) * (size_t)(mat + 1))))
+      return st;
+    GF_HIP_CHECK(ctx, launch_tknn_word(ctx, W.src, W.index, W.shift, cur, cnt, wkey.as<uint32_t>()));
+    RadixArgs r{};
+    r.tile = radix_tile();
+    r.n = cnt;
+    r.bits = pbits;
+    r.nblk = blocks;
+    r.M = K.mat.as<uint32_t>();
+    r.Ms = K.mats.as<uint32_t>();
+    for (int p = 0; p < passes; ++p) {
+      r.kin = p == 0 ? wkey.as<uint32_t>() : K.kbuf[(p - 1) & 1].as<uint32_t>();
+      r.vin = p == 0 ? cur : K.vbuf[(p - 1) & 1].as<uint32_t>();  // null: the index is the position
+      r.kout = K.kbuf[p & 1].as<uint32_t>();
+      r.vout = p == passes - 1 ? sp[next].as<uint32_t>() : K.vbuf[p & 1].as<uint32_t>();
+      r.shift = p * pbits;
+      GF_HIP_CHECK(ctx, launch_radix(ctx, 0, r, blocks));
+      if ((st = group_scan_u32(ctx, K, r.M, mat, K.mats.as<uint32_t>()))) return st;
+      GF_HIP_CHECK(ctx, launch_radix(ctx, 1, r, blocks));
+    }
+    cur = sp[next].as<uint32_t>();
+    next ^= 1;
+  }
+  *out = cur;
+  return GF_OK;
+}
+
 template <class T>
 static int read_back(gf_ctx* ctx, T* host, const void* dev, size_t count) {
   if (!host || count == 0) return GF_OK;

@@ -764,11 +764,54 @@ class TrajectoryGroups:
         _lib.check(st, self.ctx.handle, "gf_tknn_read")
         return TKNNResult(self.window, keys, dist, cells, off, x, y, ts, idx, info)
 
+    def tjoin(self, other: "TrajectoryGroups", grid: UniformGrid, r: float, single: bool = False,
+              table_slots=None) -> "TJoinResult":
+        """gf_tjoin_run: this grouped window as the ordinary side against `other`, the grouped query
+        window (PointPointTJoinQuery.run), or against itself (single=True, runSingle: `other` is these
+        groups).  The gf_tjoin object is kept and reused by later calls.  table_slots: the testing hook
+        of gf_tjoin_set_table_slots (the first table size of this call; 0: the default).  The result
+        carries `info`: rows, emitted, otraj, opoints, qtraj, qpoints, probe_passes."""
+        L = _lib.lib()
+        if getattr(self, "_tjoin", None) is None:
+            self._tjoin = C.c_void_p()
+        if table_slots is not None:
+            if not self._tjoin:
+                raise ValueError("table_slots needs an earlier tjoin() call on these groups")
+            _lib.check(L.gf_tjoin_set_table_slots(self._tjoin, int(table_slots)), None, "gf_tjoin_set_table_slots")
+        po, pq = self.window.c_struct(), other.window.c_struct()
+        st = L.gf_tjoin_run(self.handle, C.byref(po), other.handle, C.byref(pq), C.byref(grid.c_grid), float(r),
+                            _lib.TJOIN_SINGLE if single else _lib.TJOIN_PAIR, C.byref(self._tjoin))
+        _lib.check(st, self.ctx.handle, "gf_tjoin_run")
+        c = [C.c_int64() for _ in range(7)]
+        _lib.check(L.gf_tjoin_info(self._tjoin, *(C.byref(v) for v in c)), None, "gf_tjoin_info")
+        info = dict(zip(("rows", "emitted", "otraj", "opoints", "qtraj", "qpoints", "probe_passes"), (v.value for v in c)))
+        m = info["rows"]
+        okey, qkey = np.empty(m, np.int64), np.empty(m, np.int64)
+        p_first, q_latest = np.empty(m, np.uint32), np.empty(m, np.uint32)
+        emit, oslot, qslot = np.empty(m, np.uint8), np.empty(m, np.int32), np.empty(m, np.int32)
+        st = L.gf_tjoin_read_rows(self._tjoin, okey.ctypes.data, qkey.ctypes.data, p_first.ctypes.data, q_latest.ctypes.data,
+                                  emit.ctypes.data, oslot.ctypes.data, qslot.ctypes.data, m)
+        _lib.check(st, self.ctx.handle, "gf_tjoin_read_rows")
+        sides = []
+        for side, (w, nt, npt) in enumerate(((self.window, info["otraj"], info["opoints"]),
+                                             (other.window, info["qtraj"], info["qpoints"]))):
+            keys, off = np.empty(nt, np.int64), np.zeros(nt + 1, np.int64)
+            x, y, ts, idx = np.empty(npt, np.float64), np.empty(npt, np.float64), np.empty(npt, np.int64), np.empty(npt, np.uint32)
+            st = L.gf_tjoin_read_trajs(self._tjoin, side, keys.ctypes.data, off.ctypes.data, nt, x.ctypes.data, y.ctypes.data,
+                                       ts.ctypes.data, idx.ctypes.data, npt)
+            _lib.check(st, self.ctx.handle, "gf_tjoin_read_trajs")
+            sides.append(SubTrajectories(w, keys, off, x, y, ts, idx))
+        return TJoinResult(okey, qkey, p_first, q_latest, emit.astype(bool), oslot, qslot, sides[0], sides[1], info)
+
     def close(self):
         t = getattr(self, "_tknn", None)
         if t and _lib._lib is not None:
             _lib._lib.gf_tknn_destroy(t)
             self._tknn = None
+        t = getattr(self, "_tjoin", None)
+        if t and _lib._lib is not None:
+            _lib._lib.gf_tjoin_destroy(t)
+            self._tjoin = None
         h = getattr(self, "handle", None)
         if h and _lib._lib is not None:
             _lib._lib.gf_traj_groups_destroy(h)
@@ -1132,7 +1175,89 @@ class PointPointTKNNQuery:
         return self._run(window, queryPoint, queryRadius, k, True, groups)
 
 
+# ----------------------------------------------------------------------------------------
+# tJoin (the window-based trajectory join)
+# ----------------------------------------------------------------------------------------
+@dataclass
+class TJoinResult:
+    """The rows of the window-based tJoin, ascending by (ordinary rank, query rank): per row the two
+    objID keys, p_first / q_latest (window indices of the first matching ordinary point and the latest
+    matching query point), emit (both trajectories have >= 2 points) and oslot / qslot, the row's
+    trajectories in `ordinary` / `query` (SubTrajectories: each emitted trajectory whole and once; -1 where
+    emit is False).  The contract is include/geoflink_hip.h's."""
+
+    okey: np.ndarray
+    qkey: np.ndarray
+    p_first: np.ndarray
+    q_latest: np.ndarray
+    emit: np.ndarray
+    oslot: np.ndarray
+    qslot: np.ndarray
+    ordinary: SubTrajectories
+    query: SubTrajectories
+    info: dict = None
+
+    def __len__(self):
+        return len(self.okey)
+
+    @property
+    def first_point(self):
+        """The reference's firstPoint per ordinary objID: {objID key: the minimum of p_first over its rows}."""
+        out = {}
+        for k, p in zip(self.okey.tolist(), self.p_first.tolist()):
+            out[k] = min(out.get(k, p), p)
+        return out
+
+    def point_pairs(self):
+        """runSingle's / the join stage's Tuple2<Point, Point> per row as window indices: (firstPoint of the
+        row's ordinary objID, q_latest)."""
+        fp = self.first_point
+        return [(fp[k], q) for k, q in zip(self.okey.tolist(), self.q_latest.tolist())]
+
+    def trajectory_pairs(self):
+        """The emitted rows as (ordinary slot, query slot): Tuple2<LineString, LineString>."""
+        return list(zip(self.oslot[self.emit].tolist(), self.qslot[self.emit].tolist()))
+
+
+class PointPointTJoinQuery:
+    """tJoin/PointPointTJoinQuery.java windowBased (run) and commonSingle (runSingle) + TJoinQuery.java: the
+    pairs of trajectories with a point of one within joinDistance of a point of the other, each pair once,
+    each trajectory whole.  WindowBased only; the RealTime variants raise as unsupported."""
+
+    def __init__(self, conf: QueryConfiguration, index: UniformGrid = None):
+        self.conf = conf
+        self.index = index
+
+    def _check(self):
+        _require_supported(self.conf)
+        if self.conf.getQueryType() != QueryType.WindowBased:
+            raise ValueError("Not yet support")
+        if self.index is None:
+            raise ValueError("PointPointTJoinQuery needs the grid")
+
+    def run(self, ordinaryWindow: PointWindow, queryWindow: PointWindow, joinDistance: float, groups=None) -> TJoinResult:
+        """groups: (ordinary TrajectoryGroups, query TrajectoryGroups), if the caller has grouped the windows already."""
+        self._check()
+        go, gq = groups if groups is not None else (TrajectoryGroups(ordinaryWindow), TrajectoryGroups(queryWindow))
+        try:
+            return go.tjoin(gq, self.index, joinDistance)
+        finally:
+            if groups is None:
+                go.close()
+                gq.close()
+
+    def runSingle(self, window: PointWindow, joinDistance: float, groups=None) -> TJoinResult:
+        self._check()
+        g = groups if groups is not None else TrajectoryGroups(window)
+        try:
+            return g.tjoin(g, self.index, joinDistance, single=True)
+        finally:
+            if groups is None:
+                g.close()
+
+
 __all__ = [
+    "PointPointTJoinQuery", "TJoinResult",
     "PointPointTKNNQuery", "TKNNResult",
     "PointTAggregateQuery", "TAggregateResult", "TAggregateGroups", "tagg_rows",
     "PointTStatsQuery", "TStatsResult", "SubTrajectories", "TrajectoryGroups", "group_by_objid", "sub_trajectories",
