@@ -66,7 +66,8 @@ extern "C" {
 #define GF_K_TAGG        15 /* tAggregate: its own kernels (the grouping kernels count as GF_K_TRAJ_GROUP, the radix passes as GF_K_BUCKET) */
 #define GF_K_TKNN        16 /* tKnn: its own kernels (the grouping kernels count as GF_K_TRAJ_GROUP, the radix passes as GF_K_BUCKET) */
 #define GF_K_TJOIN       17 /* tJoin: its own kernels (the radix passes count as GF_K_BUCKET) */
-#define GF_K_COUNT       18
+#define GF_K_TRANGE      18 /* tRange: the contains pass (gf_trange_points / gf_trange_run; the emit counts as GF_K_TRAJ_SELECT) */
+#define GF_K_COUNT       19
 
 typedef struct gf_ctx gf_ctx;
 
@@ -864,6 +865,70 @@ int  gf_tjoin_read_trajs(gf_tjoin* t, int side, int64_t* keys, int64_t* off, int
 /* Testing: the table's size at the next gf_tjoin_run (a power of two >= 16; 0 = the default).  Results are
  * identical for any value. */
 int  gf_tjoin_set_table_slots(gf_tjoin* t, int64_t slots);
+
+/* ---- tRange / tFilter: trajectories that enter a polygon set, trajectories of an id set -------
+ * tRange/PointPolygonTRangeQuery.java and tFilter/PointTFilterQuery.java for one device-resident
+ * window.  The contract (derived from the reference and JTS 1.16.1, nothing was run on a JVM):
+ *  1. contains.  A point p is contained by a polygon iff `poly.polygon.contains(p.point.getEnvelope())`
+ *     (PointPolygonTRangeQuery.java:81,130), JTS Geometry.contains: false unless the polygon's (shell)
+ *     envelope holds p -- so a NaN or infinite coordinate is never contained -- then RectangleContains
+ *     for a rectangle (the strict interior of the box) or relate(p).isContains(), i.e. PointLocator
+ *     locates p INTERIOR: INTERIOR of the shell and neither INTERIOR nor BOUNDARY of any hole.  Both
+ *     branches agree: contained iff located INTERIOR.  A point on a shell or hole edge is NOT contained
+ *     (a range plan computes distance <= r: at a tiny positive r the closed polygon, which keeps such a
+ *     point; at r = 0 it has no candidate cells at all and returns nothing).
+ *     The ring walk is RayCrossingCounter with the exact orientation sign (RobustDeterminant).
+ *  2. The cell filter is a pure prune.  The reference keeps a point only if its gridID is among the
+ *     polygons' bbox cells (HelperClass.java:123-143).  A contained point lies strictly inside the bbox
+ *     and the cell index is monotone in the coordinate (Java's saturation included), so its cell is in
+ *     the set: filter + contains == contains, for points and polygons outside the grid too.  The plan's
+ *     cell table only skips work.
+ *  3. gf_trange_points (RealTime, :53-87): bit i of bitmap (device uint64[(n+63)/64], every word
+ *     written) = point i is contained by some polygon of the set; *count (device int64, nullable) =
+ *     the number of set bits.  Enqueued on the context stream like gf_range_run; needs x and y only.
+ *  4. gf_trange_run (WindowBased, :89-176): the trajectories (objIDs of the window grouped by
+ *     gf_traj_group) with at least one contained point, each whole, in first-occurrence order, points in
+ *     arrival order -- outputs exactly as gf_traj_select (single-point trajectories included; the caller
+ *     applies the reference's size rule).  Sync.  A trajectory already known to be hit skips its
+ *     remaining points' tests; which points were skipped depends on scheduling, the result never does.
+ *  5. gf_tfilter_run (PointTFilterQuery.java windowBased): the trajectories whose objID key is in id_set
+ *     (host, nset keys, duplicates allowed), each whole; nset == 0 = every trajectory (:92-95).  Outputs
+ *     as gf_traj_select.  Sync.
+ *  6. Errors: null plan / groups / pts / required pointer, negative capacities, npoly < 0, an invalid
+ *     grid or ring, pts that is not the grouped window, a plan and groups of different contexts:
+ *     GF_ERR_ARG before any device call.  An empty polygon set, an empty window and ntraj == 0 return
+ *     zero rows (bitmap: all zero).
+ * Not covered: Flink's triggers and sliding assignment, the RealTime tFilter's watermarking, sharding
+ * across GPUs, JNI bindings.
+ * The plan (once per continuous query): per grid cell a class -- none (no bbox covers it), test (the CSR
+ * list of the polygons whose bbox cells cover it), inside (the cell's whole coordinate extent lies
+ * strictly inside a rectangle polygon: every non-NaN point of it is contained untested) -- plus the
+ * polygons whose bbox cells leave the grid, for the points whose cell is outside it.
+ * gf_trange_plan_stats: cells per class, the list entries, and the polygons whose largest ring has at
+ * least `wide_ring` vertices: those are tested by one wave per (point, polygon) instead of one lane
+ * (gf_trange_plan_set_thresholds: wide_ring >= 1; 0 = the default, 384; results are identical for any
+ * value).  The wave path's worklist lives in the plan and only grows: n times the most wide polygons any
+ * one cell's list holds, 8 B each.  A window larger than every earlier one makes gf_trange_points and
+ * gf_trange_run synchronise the stream and allocate before they enqueue; a window whose bound exceeds
+ * 1 GiB is tested by lanes only (identical results).  gf_trange_info: of the last gf_trange_run, the points
+ * whose cell class is not none and those in inside cells (both independent of scheduling); the wide_ring
+ * in force; and wave_path = 1 iff the last gf_trange_points / gf_trange_run tested its wide polygons by
+ * waves (0: the set has none, or the worklist bound was too large).  Any output may be NULL. */
+typedef struct gf_trange_plan gf_trange_plan;
+int  gf_trange_plan_create(gf_ctx* ctx, const gf_grid* g, const gf_polygons* polys, gf_trange_plan** out);
+void gf_trange_plan_destroy(gf_trange_plan* p);
+int  gf_trange_plan_stats(const gf_trange_plan* p, int64_t* none_cells, int64_t* test_cells, int64_t* inside_cells,
+                          int64_t* list_entries, int64_t* wide_polygons);
+int  gf_trange_plan_set_thresholds(gf_trange_plan* p, int32_t wide_ring);
+int  gf_trange_points(gf_trange_plan* p, const gf_points* pts, uint64_t* bitmap, int64_t* count);
+int  gf_trange_run(gf_trange_plan* p, gf_traj_groups* g, const gf_points* pts, int64_t* keys, int64_t* off,
+                   int64_t cap_traj, double* x, double* y, int64_t* ts, uint32_t* idx, int64_t cap_pts,
+                   int64_t* ntraj_out, int64_t* npts_out);
+int  gf_trange_info(const gf_trange_plan* p, int64_t* cell_points, int64_t* inside_points, int64_t* wide_ring,
+                    int64_t* wave_path);
+int  gf_tfilter_run(gf_traj_groups* g, const gf_points* pts, const int64_t* id_set, int64_t nset, int64_t* keys,
+                    int64_t* off, int64_t cap_traj, double* x, double* y, int64_t* ts, uint32_t* idx, int64_t cap_pts,
+                    int64_t* ntraj_out, int64_t* npts_out);
 
 /* ---- pinned host memory ---------------------------------------------------------------
  * Mapped, portable host memory: kernels write kNN records straight into it (pass it as the

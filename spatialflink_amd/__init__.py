@@ -15,6 +15,7 @@ from .spatialOperators import (KNNResult, PinnedRecords, PointPointJoinQuery, Po
                                TrajectoryGroups, TStatsResult, group_by_objid, sub_trajectories,
                                PointTAggregateQuery, TAggregateGroups, TAggregateResult, tagg_rows,
                                PointPointTKNNQuery, TKNNResult, PointPointTJoinQuery, TJoinResult,
+                               PointPolygonTRangeQuery, PointTFilterQuery, TRangePlan,
                                PointPolygonRangeQuery, QueryConfiguration, QueryType, RangeResult, assign_cells,
                                bucket_by_cell, knn_merge_host, synthetic_uniform,
                                synthetic_clustered)
@@ -23,6 +24,7 @@ from .windows import SlidingKNNQuery, SlidingRangeQuery, SlidingWindows
 
 __all__ = [
     "PointPointTJoinQuery", "TJoinResult",
+    "PointPolygonTRangeQuery", "PointTFilterQuery", "TRangePlan",
     "PointPointTKNNQuery", "TKNNResult",
     "PointTAggregateQuery", "TAggregateResult", "TAggregateGroups", "tagg_rows",
     "PointTStatsQuery", "TStatsResult", "SubTrajectories", "TrajectoryGroups", "group_by_objid", "sub_trajectories",

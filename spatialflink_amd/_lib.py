@@ -43,7 +43,7 @@ FLAG_GEOJSON_CHECK = 32
 FLAG_JOIN_STREAM = 8
 (K_KNN_SCAN, K_KNN_SAMPLE, K_KNN_SELECT, K_RANGE_SCAN, K_ASSIGN, K_JOIN_PROBE, K_RANGE_TEST, K_JOIN_BUCKET,
  K_KNN_MERGE, K_CSV_PARSE, K_BUCKET, K_JOIN_COMPACT, K_TRAJ_GROUP, K_TSTATS, K_TRAJ_SELECT, K_TAGG, K_TKNN,
- K_TJOIN) = range(18)
+ K_TJOIN, K_TRANGE) = range(19)
 
 # Every symbol include/geoflink_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = [
@@ -77,6 +77,8 @@ EXPORTS = [
     "gf_tknn_run", "gf_tknn_destroy", "gf_tknn_info", "gf_tknn_read", "gf_tknn_set_thresholds",
     "gf_tjoin_run", "gf_tjoin_destroy", "gf_tjoin_info", "gf_tjoin_read_rows", "gf_tjoin_read_trajs",
     "gf_tjoin_set_table_slots",
+    "gf_trange_plan_create", "gf_trange_plan_destroy", "gf_trange_plan_stats", "gf_trange_plan_set_thresholds",
+    "gf_trange_points", "gf_trange_run", "gf_trange_info", "gf_tfilter_run",
 ]
 
 
@@ -274,6 +276,14 @@ def lib():
             "gf_tjoin_read_rows": ([P, P, P, P, P, P, P, P, i64], C.c_int),
             "gf_tjoin_read_trajs": ([P, C.c_int, P, P, i64, P, P, P, P, i64], C.c_int),
             "gf_tjoin_set_table_slots": ([P, i64], C.c_int),
+            "gf_trange_plan_create": ([P, C.POINTER(GfGrid), C.POINTER(GfPolygons), C.POINTER(P)], C.c_int),
+            "gf_trange_plan_destroy": ([P], None),
+            "gf_trange_plan_stats": ([P, pi64, pi64, pi64, pi64, pi64], C.c_int),
+            "gf_trange_plan_set_thresholds": ([P, C.c_int32], C.c_int),
+            "gf_trange_points": ([P, C.POINTER(GfPoints), P, P], C.c_int),
+            "gf_trange_run": ([P, P, C.POINTER(GfPoints), P, P, i64, P, P, P, P, i64, pi64, pi64], C.c_int),
+            "gf_trange_info": ([P, pi64, pi64, pi64, pi64], C.c_int),
+            "gf_tfilter_run": ([P, C.POINTER(GfPoints), P, i64, P, P, i64, P, P, P, P, i64, pi64, pi64], C.c_int),
         }
         for name, (argt, rest) in sig.items():
             if os.environ.get("GF_LIB_PATH") and not hasattr(L, name):

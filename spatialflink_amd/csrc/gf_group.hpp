@@ -84,3 +84,11 @@ struct gf_traj_groups : gf::KeyGroups {
   gf::DevBuf* all[23] = {&S, &T, &V, &long_list, &counters, &set, &sel, &srank, &ck, &cS, &cT, &cV, &hit, &len,
                      &row, &off, &okeys, &ooff, &ox, &oy, &ots, &oidx, nullptr};
 };
+
+namespace gf {
+// sub-trajectory emission shared by gf_traj_select, gf_trange_run and gf_tfilter_run (traj.cpp)
+int traj_check_points(gf_traj_groups* G, const gf_points* pts, const char* who);  // pts is the grouped window, with x / y / ts
+int traj_hit_clear(gf_traj_groups* G);  // G->hit[ntraj + 1] = 0 (enqueued)
+int traj_emit(gf_traj_groups* G, const gf_points* pts, int64_t* keys, int64_t* off, int64_t cap_traj, double* x, double* y,
+              int64_t* ts, uint32_t* idx, int64_t cap_pts, int64_t* ntraj_out, int64_t* npts_out);
+}  // namespace gf

@@ -594,7 +594,7 @@ struct TrajSelectArgs {
   int64_t* ots;
   uint32_t* oidx;
 };
-// stage 0: hit + lens; 1: gather
+// stage 0: hit from the bitmap; 2: lens; 1: gather
 hipError_t launch_traj_select(gf_ctx* ctx, int stage, const TrajSelectArgs& a);
 
 // tAggregate (k_tagg.hip, tagg.cpp)
@@ -818,6 +818,31 @@ struct TjoinArgs {
 // 4 run ends; 5 ordinary cell keys; 6 probe; 7 occupied flags; 8 compact; 9 rows + marks; 10 slots;
 // 11 one side's trajectory list; 12 totals; 13 one side's gather
 hipError_t launch_tjoin(gf_ctx* ctx, int stage, const TjoinArgs& a);
+
+// tRange (k_trange.hip, trange.cpp)
+struct TrangeArgs {
+  const double* x;
+  const double* y;
+  int64_t n;
+  const uint32_t* did;        // trajectory mode: dense id per point; null: point mode
+  uint32_t* hit;              // trajectory mode: [ntraj + 1], only ever 0 -> 1
+  uint64_t* bitmap;           // point mode: [(n + 63) / 64], every word written by the mark
+  int32_t grid_n;
+  double minX, minY, cl;
+  const uint8_t* cls;         // [grid_n^2] kTrNone / kTrTest / kTrInside
+  const int32_t* cand_off;    // [grid_n^2 + 1]
+  const int32_t* cand_list;
+  const int32_t* extra;       // [n_extra * 5] polygon, x0, x1, y0, y1
+  int32_t n_extra;
+  PolyView poly;
+  const uint8_t* wide;        // [npoly] 1: the wave path tests this polygon; null: every polygon by its lane
+  uint2* work;                // the wave path's worklist: (point, polygon)
+  uint32_t work_cap;          // (never exceeded: sized from the plan's largest wide list)
+  unsigned long long* ctr;    // [0] worklist entries, [1] points in non-none cells, [2] in inside cells, [3] set bits
+  int64_t* count;             // point mode, nullable: device, receives ctr[3]
+};
+// stage 0: the mark (one lane per point); 1: the wave path over the worklist; 2: the bitmap's count
+hipError_t launch_trange(gf_ctx* ctx, int stage, const TrangeArgs& a);
 
 hipError_t launch_knn_sample(gf_ctx* ctx, const KnnSampleArgs& a);
 hipError_t launch_knn_scan(gf_ctx* ctx, const KnnScanArgs& a, int blocks, int unroll, int nt);

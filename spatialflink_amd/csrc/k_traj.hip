@@ -396,6 +396,7 @@ hipError_t launch_traj_select(gf_ctx* ctx, int stage, const TrajSelectArgs& a) {
   if (stage == 0) {
     hipLaunchKernelGGL(traj_hit_kernel, dim3(traj_blocks(ctx, (uint64_t)a.n)), dim3(kBlock), 0, s, a.bitmap, a.did, a.n,
                        a.hit);
+  } else if (stage == 2) {
     hipLaunchKernelGGL(traj_lens_kernel, dim3(traj_blocks(ctx, (uint64_t)a.ntraj)), dim3(kBlock), 0, s, a.hit, a.seg_off,
                        a.ntraj, a.len);
   } else {

@@ -305,21 +305,24 @@ extern "C" int gf_tstats_run(gf_traj_groups* G, const gf_points* pts, const int6
   return GF_OK;
 }
 
-extern "C" int gf_traj_select(gf_traj_groups* G, const gf_points* pts, const uint64_t* bitmap, int64_t* keys, int64_t* off,
-                              int64_t cap_traj, double* x, double* y, int64_t* ts, uint32_t* idx, int64_t cap_pts,
-                              int64_t* ntraj_out, int64_t* npts_out) {
-  if (!G || !G->ctx) return GF_ERR_ARG;
+int gf::traj_check_points(gf_traj_groups* G, const gf_points* pts, const char* who) { return check_traj_points(G, pts, who); }
+
+int gf::traj_hit_clear(gf_traj_groups* G) {
   gf_ctx* ctx = G->ctx;
-  if (!ntraj_out || !npts_out || cap_traj < 0 || cap_pts < 0 || (G->n > 0 && !bitmap))
-    return set_err(ctx, GF_ERR_ARG, "gf_traj_select: bad argument");
-  int st = check_traj_points(G, pts, "gf_traj_select");
-  if (st) return st;
-  *ntraj_out = 0;
-  *npts_out = 0;
-  if (off) off[0] = 0;
+  const size_t m = (size_t)G->ntraj;
+  if (int st = G->hit.reserve(ctx, (m + 1) * 4)) return st;
+  GF_HIP_CHECK(ctx, hipMemsetAsync(G->hit.p, 0, (m + 1) * 4, ctx->stream));
+  return GF_OK;
+}
+
+// The sub-trajectories of G->hit (one flag per trajectory, entry ntraj zero; ntraj > 0): lengths, the
+// two scans, the gather, the read-back.  gf_traj_select, gf_trange_run (trange.cpp) and gf_tfilter_run
+// end here.  Sync.
+int gf::traj_emit(gf_traj_groups* G, const gf_points* pts, int64_t* keys, int64_t* off, int64_t cap_traj, double* x,
+                  double* y, int64_t* ts, uint32_t* idx, int64_t cap_pts, int64_t* ntraj_out, int64_t* npts_out) {
+  gf_ctx* ctx = G->ctx;
+  int st = GF_OK;
   const int64_t nt = G->ntraj, n = G->n;
-  if (nt == 0) return GF_OK;
-  if ((st = bind(ctx))) return st;
   const size_t m = (size_t)nt, np = (size_t)n;
   if ((st = G->hit.reserve(ctx, (m + 1) * 4)) || (st = G->len.reserve(ctx, (m + 1) * 4)) ||
       (st = G->row.reserve(ctx, (m + 1) * 4)) || (st = G->off.reserve(ctx, (m + 1) * 4)) ||
@@ -329,8 +332,6 @@ extern "C" int gf_traj_select(gf_traj_groups* G, const gf_points* pts, const uin
   TrajSelectArgs a{};
   a.x = pts->x; a.y = pts->y; a.ts = pts->ts;
   a.n = n; a.ntraj = nt;
-  a.bitmap = bitmap;
-  a.did = G->did.as<uint32_t>();
   a.sorted = G->kbuf[G->sorted_in].as<uint32_t>();
   a.perm = G->perm.as<uint32_t>();
   a.seg_off = G->seg_off.as<uint32_t>();
@@ -342,8 +343,7 @@ extern "C" int gf_traj_select(gf_traj_groups* G, const gf_points* pts, const uin
   a.okeys = G->okeys.as<int64_t>();
   a.ooff = G->ooff.as<uint32_t>();
   a.ox = G->ox.as<double>(); a.oy = G->oy.as<double>(); a.ots = G->ots.as<int64_t>(); a.oidx = G->oidx.as<uint32_t>();
-  GF_HIP_CHECK(ctx, hipMemsetAsync(a.hit, 0, (m + 1) * 4, ctx->stream));
-  GF_HIP_CHECK(ctx, launch_traj_select(ctx, 0, a));
+  GF_HIP_CHECK(ctx, launch_traj_select(ctx, 2, a));
   if ((st = scan_u32(G, a.hit, nt, G->row.as<uint32_t>())) || (st = scan_u32(G, a.len, nt, G->off.as<uint32_t>())))
     return st;
   GF_HIP_CHECK(ctx, launch_traj_select(ctx, 1, a));
@@ -363,4 +363,62 @@ extern "C" int gf_traj_select(gf_traj_groups* G, const gf_points* pts, const uin
   *ntraj_out = tot[0];
   *npts_out = tot[1];
   return GF_OK;
+}
+
+extern "C" int gf_traj_select(gf_traj_groups* G, const gf_points* pts, const uint64_t* bitmap, int64_t* keys, int64_t* off,
+                              int64_t cap_traj, double* x, double* y, int64_t* ts, uint32_t* idx, int64_t cap_pts,
+                              int64_t* ntraj_out, int64_t* npts_out) {
+  if (!G || !G->ctx) return GF_ERR_ARG;
+  gf_ctx* ctx = G->ctx;
+  if (!ntraj_out || !npts_out || cap_traj < 0 || cap_pts < 0 || (G->n > 0 && !bitmap))
+    return set_err(ctx, GF_ERR_ARG, "gf_traj_select: bad argument");
+  int st = check_traj_points(G, pts, "gf_traj_select");
+  if (st) return st;
+  *ntraj_out = 0;
+  *npts_out = 0;
+  if (off) off[0] = 0;
+  if (G->ntraj == 0) return GF_OK;
+  if ((st = bind(ctx)) || (st = traj_hit_clear(G))) return st;
+  TrajSelectArgs a{};
+  a.n = G->n;
+  a.bitmap = bitmap;
+  a.did = G->did.as<uint32_t>();
+  a.hit = G->hit.as<uint32_t>();
+  GF_HIP_CHECK(ctx, launch_traj_select(ctx, 0, a));
+  return traj_emit(G, pts, keys, off, cap_traj, x, y, ts, idx, cap_pts, ntraj_out, npts_out);
+}
+
+// tFilter/PointTFilterQuery.java windowBased: the trajectories whose key is in the set, whole; an empty
+// set is every trajectory (:92-95).  The membership test is gf_tstats_run's binary search.
+extern "C" int gf_tfilter_run(gf_traj_groups* G, const gf_points* pts, const int64_t* id_set, int64_t nset, int64_t* keys,
+                              int64_t* off, int64_t cap_traj, double* x, double* y, int64_t* ts, uint32_t* idx,
+                              int64_t cap_pts, int64_t* ntraj_out, int64_t* npts_out) {
+  if (!G || !G->ctx) return GF_ERR_ARG;
+  gf_ctx* ctx = G->ctx;
+  if (!ntraj_out || !npts_out || cap_traj < 0 || cap_pts < 0 || nset < 0 || (nset > 0 && !id_set))
+    return set_err(ctx, GF_ERR_ARG, "gf_tfilter_run: bad argument");
+  int st = check_traj_points(G, pts, "gf_tfilter_run");
+  if (st) return st;
+  *ntraj_out = 0;
+  *npts_out = 0;
+  if (off) off[0] = 0;
+  const int64_t nt = G->ntraj;
+  if (nt == 0) return GF_OK;
+  if ((st = bind(ctx)) || (st = traj_hit_clear(G))) return st;
+  uint32_t* hit = G->hit.as<uint32_t>();
+  if (nset == 0) {
+    GF_HIP_CHECK(ctx, hipMemsetD32Async((hipDeviceptr_t)hit, 1, (size_t)nt, ctx->stream));
+  } else {
+    std::vector<int64_t> set(id_set, id_set + nset);
+    std::sort(set.begin(), set.end());
+    set.erase(std::unique(set.begin(), set.end()), set.end());
+    if ((st = G->set.reserve(ctx, set.size() * 8))) return st;
+    // (a pageable source: the copy has left `set` when the call returns)
+    GF_HIP_CHECK(ctx, hipMemcpy(G->set.p, set.data(), set.size() * 8, hipMemcpyHostToDevice));
+    TStatsArgs a{};
+    a.ntraj = nt;
+    GF_HIP_CHECK(ctx, launch_tstats_filter(ctx, a, G->keys.as<int64_t>(), G->set.as<int64_t>(), (int64_t)set.size(), hit,
+                                           nullptr, nullptr, nullptr, nullptr, nullptr, 0));
+  }
+  return traj_emit(G, pts, keys, off, cap_traj, x, y, ts, idx, cap_pts, ntraj_out, npts_out);
 }

@@ -723,17 +723,48 @@ class TrajectoryGroups:
 
     def select(self, bitmap):
         """Sub-trajectories of a device hit bitmap (torch int64 words) -> SubTrajectories."""
-        nt, n = self.ntraj, self.n
+        pts = self.window.c_struct()
+        return self._emit(lambda *a: _lib.lib().gf_traj_select(self.handle, C.byref(pts), bitmap.data_ptr() if self.n else None,
+                                                               *a), "gf_traj_select")
+
+    def _emit(self, call, name, cap_traj=None, cap_pts=None):
+        """Host arrays of a gf_traj_select-shaped call -> SubTrajectories (at most cap_traj / cap_pts
+        written; `totals` = the full counts)."""
+        nt = self.ntraj if cap_traj is None else int(cap_traj)
+        n = self.n if cap_pts is None else int(cap_pts)
         keys, off = np.empty(nt, np.int64), np.zeros(nt + 1, np.int64)
         x, y, ts, idx = np.empty(n, np.float64), np.empty(n, np.float64), np.empty(n, np.int64), np.empty(n, np.uint32)
         m, npts = C.c_int64(), C.c_int64()
+        st = call(keys.ctypes.data, off.ctypes.data, nt, x.ctypes.data, y.ctypes.data, ts.ctypes.data, idx.ctypes.data, n,
+                  C.byref(m), C.byref(npts))
+        _lib.check(st, self.ctx.handle, name)
+        k, q = min(m.value, nt), min(npts.value, n)
+        out = SubTrajectories(self.window, keys[:k], off[:k + 1], x[:q], y[:q], ts[:q], idx[:q])
+        out.totals = (m.value, npts.value)
+        return out
+
+    def trange(self, grid: UniformGrid, polygons, plan: "TRangePlan" = None, cap_traj=None, cap_pts=None) -> "SubTrajectories":
+        """gf_trange_run: the trajectories of this grouped window with a point CONTAINED (JTS contains:
+        located INTERIOR; a point on an edge is not) by some polygon, each whole.  plan: a TRangePlan of
+        (grid, polygons) to reuse (default: one is built for the call and destroyed)."""
+        own = plan is None
+        if own:
+            plan = TRangePlan(self.ctx, grid, polygons)
+        try:
+            pts = self.window.c_struct()
+            return self._emit(lambda *a: _lib.lib().gf_trange_run(plan.handle, self.handle, C.byref(pts), *a), "gf_trange_run",
+                              cap_traj, cap_pts)
+        finally:
+            if own:
+                plan.close()
+
+    def tfilter(self, trajIDSet=(), cap_traj=None, cap_pts=None) -> "SubTrajectories":
+        """gf_tfilter_run: the trajectories whose objID key is in trajIDSet (keys), each whole; an empty
+        set = every trajectory (PointTFilterQuery.java:92-95)."""
+        ids = np.ascontiguousarray(np.asarray(list(trajIDSet), np.int64))
         pts = self.window.c_struct()
-        st = _lib.lib().gf_traj_select(self.handle, C.byref(pts), bitmap.data_ptr() if n else None, keys.ctypes.data,
-                                       off.ctypes.data, nt, x.ctypes.data, y.ctypes.data, ts.ctypes.data,
-                                       idx.ctypes.data, n, C.byref(m), C.byref(npts))
-        _lib.check(st, self.ctx.handle, "gf_traj_select")
-        k, q = m.value, npts.value
-        return SubTrajectories(self.window, keys[:k], off[:k + 1], x[:q], y[:q], ts[:q], idx[:q])
+        return self._emit(lambda *a: _lib.lib().gf_tfilter_run(self.handle, C.byref(pts), ids.ctypes.data if len(ids) else None,
+                                                               len(ids), *a), "gf_tfilter_run", cap_traj, cap_pts)
 
     def tknn(self, grid: UniformGrid, queryPoint, queryRadius: float, k: int, naive: bool = False, big_cell=None,
              cap_rows=None, cap_pts=None) -> "TKNNResult":
@@ -944,6 +975,124 @@ def sub_trajectories(window: PointWindow, hits) -> SubTrajectories:
         return g.select(bitmap)
     finally:
         g.close()
+
+
+# ----------------------------------------------------------------------------------------
+# tRange / tFilter (trajectories that enter a polygon set; trajectories of an id set)
+# ----------------------------------------------------------------------------------------
+class TRangePlan:
+    """gf_trange_plan of (grid, polygon set) on one context: built once per continuous query."""
+
+    def __init__(self, ctx, grid: UniformGrid, polygons):
+        self.ctx = ctx
+        self._owned = True
+        ps = polygons if isinstance(polygons, PolygonSet) else PolygonSet(polygons)
+        cs = ps.c_struct()
+        self.handle = C.c_void_p()
+        st = _lib.lib().gf_trange_plan_create(ctx.handle, C.byref(grid.c_grid), C.byref(cs), C.byref(self.handle))
+        _lib.check(st, ctx.handle, "gf_trange_plan_create")
+
+    def stats(self) -> dict:
+        c = [C.c_int64() for _ in range(5)]
+        _lib.check(_lib.lib().gf_trange_plan_stats(self.handle, *(C.byref(v) for v in c)), None, "gf_trange_plan_stats")
+        return dict(zip(("none_cells", "test_cells", "inside_cells", "list_entries", "wide_polygons"), (v.value for v in c)))
+
+    def set_thresholds(self, wide_ring: int = 0):
+        """Testing / tuning: polygons whose largest ring has at least `wide_ring` vertices are tested by a
+        wave per (point, polygon) (0: the default).  Results are identical for any value."""
+        _lib.check(_lib.lib().gf_trange_plan_set_thresholds(self.handle, int(wide_ring)), self.ctx.handle,
+                   "gf_trange_plan_set_thresholds")
+
+    def info(self) -> dict:
+        c = [C.c_int64() for _ in range(4)]
+        _lib.check(_lib.lib().gf_trange_info(self.handle, *(C.byref(v) for v in c)), None, "gf_trange_info")
+        return dict(zip(("cell_points", "inside_points", "wide_ring", "wave_path"), (v.value for v in c)))
+
+    def points(self, window: PointWindow) -> RangeResult:
+        """gf_trange_points: the contained points of `window` as a RangeResult (bitmap + count)."""
+        import torch
+
+        words = max(1, (window.n + 63) // 64)
+        bitmap = torch.zeros(words, dtype=torch.int64, device=window.x.device)
+        counts = torch.zeros(2, dtype=torch.int64, device=window.x.device)
+        pts = window.c_struct()
+        st = _lib.lib().gf_trange_points(self.handle, C.byref(pts), bitmap.data_ptr(), counts.data_ptr())
+        _lib.check(st, self.ctx.handle, "gf_trange_points")
+        return RangeResult(window, bitmap, counts, None, 1, self.ctx)
+
+    def close(self):
+        h = getattr(self, "handle", None)
+        if h and getattr(self, "_owned", False) and _lib._lib is not None:
+            _lib._lib.gf_trange_plan_destroy(h)
+            self.handle = C.c_void_p()
+
+    __del__ = close
+
+
+class PointPolygonTRangeQuery(SpatialOperator):
+    """tRange/PointPolygonTRangeQuery.java.  WindowBased (:89-176): the trajectories with a point contained
+    by some polygon of the set, each whole -> SubTrajectories.  RealTime (:53-87): the contained points
+    -> RangeResult.  contains is JTS's: a point on a shell or hole edge is not contained.  Plans are
+    cached by the polygon set's digest."""
+
+    _destroy_name = "gf_trange_plan_destroy"
+
+    def plan(self, device: int, polygonSet) -> TRangePlan:
+        ctx = _lib.context(device)
+        ps = polygonSet if isinstance(polygonSet, PolygonSet) else PolygonSet(polygonSet)
+        key = (ctx.device, ps.digest())
+        h = self._plans.get(key)
+        if h is None:
+            p = TRangePlan(ctx, self.index, ps)
+            h, p._owned = p.handle, False  # the cache owns it
+            self._plans.put(key, h)
+        view = TRangePlan.__new__(TRangePlan)  # a borrowed view: close() never destroys
+        view.ctx, view.handle, view._owned = ctx, h, False
+        return view
+
+    def run(self, window: PointWindow, polygonSet, groups: "TrajectoryGroups" = None):
+        qt = self.conf.getQueryType()
+        if qt not in (QueryType.WindowBased, QueryType.RealTime):
+            raise ValueError("Not yet support")
+        plan = self.plan(window.x.device.index, polygonSet)
+        if qt == QueryType.RealTime:
+            return plan.points(window)
+        g = groups if groups is not None else TrajectoryGroups(window)
+        try:
+            return g.trange(self.index, polygonSet, plan=plan)
+        finally:
+            if groups is None:
+                g.close()
+
+    def __del__(self):
+        plans = getattr(self, "_plans", None)
+        if plans is not None:
+            plans.close()
+
+
+class PointTFilterQuery:
+    """tFilter/PointTFilterQuery.java windowBased: the trajectories whose objID is in trajIDSet (Strings or
+    keys), each whole; an empty set = every trajectory (:92-95).  A String the window's dictionary never
+    saw matches nothing."""
+
+    def __init__(self, conf: QueryConfiguration, index: UniformGrid = None):
+        self.conf = conf
+        self.index = index
+
+    def run(self, window: PointWindow, trajIDSet=(), groups: "TrajectoryGroups" = None) -> "SubTrajectories":
+        if self.conf.getQueryType() != QueryType.WindowBased:
+            raise ValueError("Not yet support")
+        ids = _traj_id_keys(window, trajIDSet)
+        if ids is not None and len(ids) == 0:  # a non-empty set none of whose Strings the window can hold
+            e = np.empty(0)
+            return SubTrajectories(window, e.astype(np.int64), np.zeros(1, np.int64), e, e.copy(), e.astype(np.int64),
+                                   e.astype(np.uint32))
+        g = groups if groups is not None else TrajectoryGroups(window)
+        try:
+            return g.tfilter(() if ids is None else ids)
+        finally:
+            if groups is None:
+                g.close()
 
 
 # ----------------------------------------------------------------------------------------
@@ -1258,6 +1407,7 @@ class PointPointTJoinQuery:
 
 __all__ = [
     "PointPointTJoinQuery", "TJoinResult",
+    "PointPolygonTRangeQuery", "PointTFilterQuery", "TRangePlan",
     "PointPointTKNNQuery", "TKNNResult",
     "PointTAggregateQuery", "TAggregateResult", "TAggregateGroups", "tagg_rows",
     "PointTStatsQuery", "TStatsResult", "SubTrajectories", "TrajectoryGroups", "group_by_objid", "sub_trajectories",
