@@ -62,22 +62,33 @@ void* ctx_pinned(gf_ctx* ctx, size_t bytes, int* status) {
   return ctx->pinned;
 }
 
-static hipEvent_t take_event(gf_ctx* ctx) {
-  if (!ctx->pool.empty()) {
-    hipEvent_t e = ctx->pool.back();
-    ctx->pool.pop_back();
+// Two kinds of event, two pools; an event of one kind is never handed out as the other.
+//   timing    (KTimer): timestamps only.  Without the system-scope fence a record neither writes
+//             back nor invalidates the caches under the launches around it.
+//   ordering  (gf_ctx_join / gf_ctx_fork): order streams of this one device, so a device-scope
+//             release is enough, and no timestamp is taken.
+// Nothing read the host through either: records in mapped pinned memory are read after a stream
+// or device synchronise, which releases to system scope itself.
+static hipEvent_t take_event(std::vector<hipEvent_t>& pool, unsigned flags) {
+  if (!pool.empty()) {
+    hipEvent_t e = pool.back();
+    pool.pop_back();
     return e;
   }
   hipEvent_t e = nullptr;
-  hipEventCreate(&e);
+  hipEventCreateWithFlags(&e, flags);
   return e;
+}
+static hipEvent_t take_timing_event(gf_ctx* ctx) { return take_event(ctx->pool, hipEventDisableSystemFence); }
+static hipEvent_t take_order_event(gf_ctx* ctx) {
+  return take_event(ctx->order_pool, hipEventDisableTiming | hipEventReleaseToDevice);
 }
 
 KTimer::KTimer(gf_ctx* c, int k) : ctx(c), kid(k) {
   if (!(ctx->timing & (1 << k))) return;
   if (ctx->timing_period > 1 && (ctx->timing_seq[k]++ % ctx->timing_period) != 0) return;
-  a = take_event(ctx);
-  b = take_event(ctx);
+  a = take_timing_event(ctx);
+  b = take_timing_event(ctx);
   hipEventRecord(a, ctx->stream);
 }
 KTimer::~KTimer() {
@@ -225,6 +236,7 @@ extern "C" void gf_ctx_destroy(gf_ctx* ctx) {
   if (ctx->geojson_check) hipFree(ctx->geojson_check);
   for (auto& e : ctx->pending) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
   for (auto e : ctx->pool) hipEventDestroy(e);
+  for (auto e : ctx->order_pool) hipEventDestroy(e);
   if (ctx->scratch) hipFree(ctx->scratch);
   if (ctx->pinned) hipHostFree(ctx->pinned);
   if (ctx->own_stream) hipStreamDestroy(ctx->own_stream);
@@ -250,10 +262,10 @@ extern "C" int gf_ctx_join(gf_ctx* ctx) {
   if (st) return st;
   for (hipStream_t a : {ctx->aux, ctx->aux2}) {
     if (!a) continue;
-    hipEvent_t ev = take_event(ctx);
+    hipEvent_t ev = take_order_event(ctx);
     GF_HIP_CHECK(ctx, hipEventRecord(ev, a));
     GF_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ev, 0));
-    ctx->pool.push_back(ev);
+    ctx->order_pool.push_back(ev);
   }
   return GF_OK;
 }
@@ -263,11 +275,11 @@ extern "C" int gf_ctx_fork(gf_ctx* ctx) {
   if (!ctx->aux) return GF_OK;
   int st = bind(ctx);
   if (st) return st;
-  hipEvent_t ev = take_event(ctx);
+  hipEvent_t ev = take_order_event(ctx);
   GF_HIP_CHECK(ctx, hipEventRecord(ev, ctx->stream));
   for (hipStream_t a : {ctx->aux, ctx->aux2})
     if (a) GF_HIP_CHECK(ctx, hipStreamWaitEvent(a, ev, 0));
-  ctx->pool.push_back(ev);
+  ctx->order_pool.push_back(ev);
   return GF_OK;
 }
 

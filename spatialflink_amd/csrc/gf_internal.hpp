@@ -24,7 +24,8 @@ struct gf_ctx {
   int64_t timing_seq[GF_K_COUNT] = {};
   struct Ev { hipEvent_t a, b; int kid; };
   std::vector<Ev> pending;
-  std::vector<hipEvent_t> pool;
+  std::vector<hipEvent_t> pool;        // timing events (KTimer), free
+  std::vector<hipEvent_t> order_pool;  // stream-ordering events (gf_ctx_join / gf_ctx_fork), free
   double acc_ms[GF_K_COUNT] = {};
   int64_t acc_n[GF_K_COUNT] = {};
   // grow-only scratch (device) and pinned host staging
