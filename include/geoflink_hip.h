@@ -115,6 +115,15 @@ typedef struct {
   const double* vy;
 } gf_polygons;
 
+/* Query linestrings (host CSR): line l owns vertices [vert_off[l], vert_off[l+1]), >= 2 each.  An
+ * open chain: repeated vertices and first == last are legal and mean nothing special. */
+typedef struct {
+  int32_t nline;
+  const int32_t* vert_off;
+  const double* vx;
+  const double* vy;
+} gf_linestrings;
+
 /* ---- library / context ------------------------------------------------------------- */
 int         gf_abi_version(void);
 /* Build identity (no reference counterpart): the compile-time tuning / experiment defines every
@@ -623,6 +632,36 @@ int gf_join_ppoly_run(gf_range_plan* plan, const gf_grid* ugrid, const gf_points
 int gf_join_ppoly(gf_ctx* ctx, const gf_grid* ugrid, const gf_grid* qgrid, const gf_points* points,
                   const gf_polygons* polys, double r, int approximate, int metric, uint32_t* pairs,
                   int64_t cap, int64_t* npairs);
+
+/* ---- query linestrings over point windows -----------------------------------------------
+ * PointLineStringRangeQuery (range/PointLineStringRangeQuery.java:100-172),
+ * PointLineStringKNNQuery (knn/PointLineStringKNNQuery.java, windowBased) and
+ * PointLineStringJoinQuery (join/PointLineStringJoinQuery.java, windowBased): the point-polygon
+ * window paths with the geometry renamed -- the cell sets come from the line's bbox cells
+ * (UniformGrid.java:208-222, 413-426; JoinQuery.java:117-137), the approximate distance is the bbox
+ * distance (DistanceFunctions.java:203-255) -- and one other exact distance: Point.distance(LineString)
+ * (DistanceFunctions.java:38-42) is the minimum of Distance.pointToSegment over the open chain, with
+ * no containment step (a point inside a closed chain is at its distance to the nearest segment).
+ * The plans are ordinary gf_range_plan / gf_knn_plan objects: gf_range_run, gf_range_run_batch,
+ * gf_range_plan_stats, the tuning calls, gf_range_sliding_*, gf_join_ppoly_run (the pair list's
+ * second column is then the line index), gf_knn_enqueue / decode / run (pipeline depth <= 2 as for
+ * polygon plans), gf_knn_sliding_* and the merges take them unchanged.  Errors as the polygon
+ * creators: null or negative counts, a bad metric or a line of < 2 vertices -> GF_ERR_ARG; kNN takes
+ * exactly one line; an empty set is a valid plan that matches nothing. */
+int gf_range_pls_plan_create(gf_ctx* ctx, const gf_grid* g, const gf_linestrings* lines, double r,
+                             int approximate, int metric, gf_range_plan** out);
+int gf_knn_pls_plan_create(gf_ctx* ctx, const gf_grid* g, const gf_linestrings* lines /* nline == 1 */, double r,
+                           int32_t k, int approximate, int metric, gf_knn_plan** out);
+int gf_join_pls_plan_create(gf_ctx* ctx, const gf_grid* qgrid, const gf_linestrings* lines, double r,
+                            int approximate, int metric, gf_range_plan** out);
+int gf_join_pls(gf_ctx* ctx, const gf_grid* ugrid, const gf_grid* qgrid, const gf_points* points,
+                const gf_linestrings* lines, double r, int approximate, int metric, uint32_t* pairs,
+                int64_t cap, int64_t* npairs);
+/* Testing / tuning of a linestring plan's exact distance: 0 = chains longer than one run of segments
+ * skip the runs whose envelope is provably farther than the bound (default), 1 = the plain segment
+ * loop.  Results never depend on it.  GF_ERR_ARG for another mode or a plan that is no linestring plan. */
+int gf_range_plan_set_chain_mode(gf_range_plan* plan, int mode);
+int gf_knn_plan_set_chain_mode(gf_knn_plan* plan, int mode);
 
 /* ---- trajectories -----------------------------------------------------------------------
  * The reference's t* operators (TStatsQuery, PointPolygonTRangeQuery, PointPointTKNNQuery, ...)

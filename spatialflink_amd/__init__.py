@@ -5,17 +5,19 @@ for gfx950 behind the C ABI in include/geoflink_hip.h; this package is the host-
 mirror of the reference operator API (UniformGrid, Point, Polygon, QueryConfiguration,
 PointPointRangeQuery, PointPolygonRangeQuery, PointPointKNNQuery, PointPointJoinQuery,
 PointPolygonKNNQuery, PointPolygonJoinQuery, PointTStatsQuery, PointTAggregateQuery,
-PointPointTKNNQuery, PointPointTJoinQuery).
+PointPointTKNNQuery, PointPointTJoinQuery, LineString and the PointLineString{Range,KNN,Join}Query
+operators).
 """
 from . import _lib, sharding
 from .spatialIndices import UniformGrid, generateCellIDStr, getIntCellIndices, padLeadingZeroesToInt
-from .spatialObjects import ObjIdDict, Point, PointWindow, Polygon, PolygonSet
+from .spatialObjects import LineString, LineStringSet, ObjIdDict, Point, PointWindow, Polygon, PolygonSet
 from .spatialOperators import (KNNResult, PinnedRecords, PointPointJoinQuery, PointPointKNNQuery, PointPointRangeQuery,
                                PointPolygonJoinQuery, PointPolygonKNNQuery, PointTStatsQuery, SubTrajectories,
                                TrajectoryGroups, TStatsResult, group_by_objid, sub_trajectories,
                                PointTAggregateQuery, TAggregateGroups, TAggregateResult, tagg_rows,
                                PointPointTKNNQuery, TKNNResult, PointPointTJoinQuery, TJoinResult,
                                PointPolygonTRangeQuery, PointTFilterQuery, TRangePlan,
+                               PointLineStringJoinQuery, PointLineStringKNNQuery, PointLineStringRangeQuery,
                                PointPolygonRangeQuery, QueryConfiguration, QueryType, RangeResult, assign_cells,
                                bucket_by_cell, knn_merge_host, synthetic_uniform,
                                synthetic_clustered)
@@ -23,6 +25,7 @@ from .spatialStreams import Deserialization
 from .windows import SlidingKNNQuery, SlidingRangeQuery, SlidingWindows
 
 __all__ = [
+    "LineString", "LineStringSet", "PointLineStringRangeQuery", "PointLineStringKNNQuery", "PointLineStringJoinQuery",
     "PointPointTJoinQuery", "TJoinResult",
     "PointPolygonTRangeQuery", "PointTFilterQuery", "TRangePlan",
     "PointPointTKNNQuery", "TKNNResult",

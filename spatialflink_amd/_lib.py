@@ -63,6 +63,8 @@ EXPORTS = [
     "gf_objid_dict_create", "gf_objid_dict_destroy", "gf_ctx_objid_dict", "gf_objid_dict_size", "gf_objid_intern",
     "gf_objid_decode", "gf_join_pp", "gf_join_pp_async",
     "gf_join_ppoly_plan_create", "gf_join_ppoly_run", "gf_join_ppoly",
+    "gf_range_pls_plan_create", "gf_knn_pls_plan_create", "gf_join_pls_plan_create", "gf_join_pls",
+    "gf_range_plan_set_chain_mode", "gf_knn_plan_set_chain_mode",
     "gf_window_create",
     "gf_window_destroy", "gf_window_upload", "gf_window_points", "gf_synth_uniform", "gf_pinned_alloc",
     "gf_pinned_free", "gf_knn_string_record_bytes", "gf_knn_attach_strings", "gf_knn_merge_dev_strings",
@@ -95,6 +97,10 @@ class GfPoints(C.Structure):
 class GfPolygons(C.Structure):
     _fields_ = [("npoly", C.c_int32), ("ring_off", C.c_void_p), ("vert_off", C.c_void_p),
                 ("vx", C.c_void_p), ("vy", C.c_void_p)]
+
+
+class GfLineStrings(C.Structure):
+    _fields_ = [("nline", C.c_int32), ("vert_off", C.c_void_p), ("vx", C.c_void_p), ("vy", C.c_void_p)]
 
 
 class GfKnnHeader(C.Structure):
@@ -222,6 +228,16 @@ def lib():
             "gf_join_ppoly_run": ([P, C.POINTER(GfGrid), C.POINTER(GfPoints), P, i64, pi64], C.c_int),
             "gf_join_ppoly": ([P, C.POINTER(GfGrid), C.POINTER(GfGrid), C.POINTER(GfPoints), C.POINTER(GfPolygons), d,
                                C.c_int, C.c_int, P, i64, pi64], C.c_int),
+            "gf_range_pls_plan_create": ([P, C.POINTER(GfGrid), C.POINTER(GfLineStrings), d, C.c_int, C.c_int,
+                                          C.POINTER(P)], C.c_int),
+            "gf_knn_pls_plan_create": ([P, C.POINTER(GfGrid), C.POINTER(GfLineStrings), d, i32, C.c_int, C.c_int,
+                                        C.POINTER(P)], C.c_int),
+            "gf_join_pls_plan_create": ([P, C.POINTER(GfGrid), C.POINTER(GfLineStrings), d, C.c_int, C.c_int,
+                                         C.POINTER(P)], C.c_int),
+            "gf_join_pls": ([P, C.POINTER(GfGrid), C.POINTER(GfGrid), C.POINTER(GfPoints), C.POINTER(GfLineStrings), d,
+                             C.c_int, C.c_int, P, i64, pi64], C.c_int),
+            "gf_range_plan_set_chain_mode": ([P, C.c_int], C.c_int),
+            "gf_knn_plan_set_chain_mode": ([P, C.c_int], C.c_int),
             "gf_window_create": ([P, i64, C.POINTER(P)], C.c_int),
             "gf_window_destroy": ([P], None),
             "gf_window_upload": ([P, P, P, P, P, i64], C.c_int),

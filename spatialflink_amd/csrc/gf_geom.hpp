@@ -172,4 +172,62 @@ __device__ __forceinline__ bool env_holds(const double* bb, double px, double py
   return px >= bb[0] && px <= bb[2] && py >= bb[1] && py <= bb[3];
 }
 
+// Point.distance(LineString) -- DistanceFunctions.java:38-42: a JTS DistanceOp with no containment
+// step, i.e. with md = Double.MAX_VALUE once per line: for each segment of the OPEN chain in order,
+// d = Distance.pointToSegment; if (d < md) md = d; if (md <= 0) stop.  (DistanceOp's one envelope
+// check per line compares against md = MAX and never skips.)  A NaN d never compares below md, so
+// a point with a NaN coordinate is at DBL_MAX.  No locate_in_ring, no sign_det2x2: a point inside a
+// closed chain is at its distance to the nearest segment.
+//
+// Sub-chain envelopes.  The host cuts every chain into runs of kChainRun consecutive segments and
+// uploads one envelope per run (ChainView::run_env, in env_far's x1, y1, x2, y2 order); the loop
+// visits the runs in order and skips a run when env_far(run envelope, p, bound) holds.  Every
+// segment of a run lies inside the run's envelope, so the envelope-prune argument above holds per
+// run: a segment's computed distance is within ~16 eps x (coordinate scale) of its true distance,
+// which is >= the true envelope distance, and env_far's margin exceeds that by orders of
+// magnitude -- a skipped run holds no segment whose COMPUTED distance is <= bound.
+//   VALUE == false (range, join: only d <= r is asked), bound = r: the visited segments include
+//     every one with computed d <= r, so (result <= r) equals the plain loop's (min <= r); the walk
+//     ends after the first run that brought md to <= r (the returned value is then some segment's
+//     distance <= r, not necessarily the minimum -- the callers only compare it with r).
+//   VALUE == true (kNN: the value is stored), bound = min(md so far, T): a skipped segment has
+//     computed d > md (it would not lower the minimum) or d > T.  So whenever the plain minimum is
+//     <= T the result is that minimum bit for bit; otherwise both are > T and the caller drops the
+//     point (every caller tests d <= T before using d).
+// The early stop at md <= 0 returns the same 0 either way (a segment at 0 is never skipped for a
+// bound >= 0; for a negative bound every result is > bound).  A null run_off (mode 1 of
+// gf_*_plan_set_chain_mode), a line of at most kChainPlainRuns runs (kChainPlainRunsValue where the
+// value is kept), or a NaN coordinate takes the plain loop.
+//
+// (kChainRun: gf_internal.hpp, with the reasoning for its value.)
+template <bool VALUE>
+static __device__ __forceinline__ double chain_distance(double px, double py, const ChainView& a, int l, double bound) {
+  const int v0 = a.vert_off[l], nseg = a.vert_off[l + 1] - v0 - 1;
+  double md = 1.7976931348623157e308;
+  if (a.run_off && px == px && py == py) {
+    const int r0 = a.run_off[l], nrun = a.run_off[l + 1] - r0;
+    if (nrun > (VALUE ? kChainPlainRunsValue : kChainPlainRuns)) {
+      for (int rn = 0; rn < nrun; ++rn) {
+        const double b = VALUE ? (md < bound ? md : bound) : bound;
+        if (env_far(a.run_env + 4 * (size_t)(r0 + rn), px, py, b)) continue;
+        const int s0 = rn * kChainRun, s1 = s0 + kChainRun < nseg ? s0 + kChainRun : nseg;
+        for (int i = s0; i < s1; ++i) {
+          const double d = point_to_segment(px, py, a.vx[v0 + i], a.vy[v0 + i], a.vx[v0 + i + 1], a.vy[v0 + i + 1],
+                                            a.metric);
+          if (d < md) md = d;
+          if (md <= 0.0) return md;
+        }
+        if (!VALUE && md <= bound) return md;  // the decision is made: some segment is within the bound
+      }
+      return md;
+    }
+  }
+  for (int i = 0; i < nseg; ++i) {
+    const double d = point_to_segment(px, py, a.vx[v0 + i], a.vy[v0 + i], a.vx[v0 + i + 1], a.vy[v0 + i + 1], a.metric);
+    if (d < md) md = d;
+    if (md <= 0.0) return md;
+  }
+  return md;
+}
+
 }  // namespace gf

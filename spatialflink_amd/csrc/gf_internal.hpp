@@ -213,6 +213,32 @@ struct PolyView {
   const uint8_t* rect;     // [npoly] 1: one-ring axis-aligned rectangle (nullable)
 };
 
+// one linestring set in device memory (CSR: line -> vertices; open chains of >= 2 vertices).  A
+// linestring plan is a polygon plan with one "ring" per object, and its arguments travel in the
+// polygon fields (RangeArgs, KnnPolyArgs::poly) so that the polygon kernels' argument blocks keep
+// their layout: ring_off carries run_off, ring_env carries run_env, rect is null.
+// kChainRun = 32, from the code: a segment costs about four envelope tests (two fp64 divisions
+// and a square root against a dozen adds, compares and multiplies), so a point at bound b of a
+// chain whose runs are w wide pays about (2 b + w) / w runs of R segments plus nruns / 4 segment
+// costs for the envelope tests.  For a line of 4,096 segments over 100 cells at b = one cell that is
+// 162 segment costs at R = 16, 146 at R = 32, 162 at R = 64 (of 4,096 for the plain loop); the
+// envelopes add 32 B per 512 B of vertices.  Unmeasured beyond tools/bench_linestring.py's one setting.
+constexpr int kChainRun = 32;
+// Lines of at most this many runs take the plain loop: 2 where only d <= r is asked (range, join), 4 where
+// the value is kept (kNN).  Measured (tools/bench_linestring.py, 10M points), skipping runs
+// against the plain loop: at 64 segments (two runs) range +3%, kNN -4%; at 128 (four runs) range 1.24x,
+// kNN 0.88x; at 256 range 2.3x, kNN 1.4x.  Lengths in between were not measured.
+constexpr int kChainPlainRuns = 2;
+constexpr int kChainPlainRunsValue = 4;
+struct ChainView {
+  const int32_t* run_off;  // [nline+1] runs of kChainRun segments per line (null: the plain segment loop)
+  const int32_t* vert_off;
+  const double* vx;
+  const double* vy;
+  const double* run_env;   // [nruns*4] x1, y1, x2, y2 (env_far's order)
+  int metric;
+};
+
 // polygon-query kNN (PointPolygonKNNQuery): scan / sample arguments
 struct KnnPolyArgs {
   const double* x;
@@ -300,12 +326,12 @@ struct RangeArgs {
   const double* qx;          // point-point queries (device)
   const double* qy;
   int32_t npoly;
-  const int32_t* ring_off;   // polygons (device)
+  const int32_t* ring_off;   // polygons (device); a linestring plan: the lines' run offsets (null: plain loop)
   const int32_t* vert_off;
   const double* vx;
   const double* vy;
   const double* bbox;        // [npoly*4] x1, y1, x2, y2 (shell envelope)
-  const double* ring_env;    // [nrings*4] minx, maxx, miny, maxy
+  const double* ring_env;    // [nrings*4] minx, maxx, miny, maxy; a linestring plan: [runs*4] x1, y1, x2, y2
   // deferred candidate tests (table modes): scan appends, range_test_kernel drains
   uint32_t* queue;           // [blocks * seg_cap] point indices, a segment per scan block; null => inline
   uint32_t* queue_count;     // [blocks] entries per segment
@@ -875,13 +901,14 @@ constexpr int32_t kMaxKLarge = 1 << 24;  // largest k of the sorted (k > kMaxK) 
 // the exact record (status 0) of one window through the sorted path, any k (knn.cpp)
 int knn_exact_record(gf_knn_plan* P, const gf_points* pts, void* result);
 
-hipError_t launch_knn_poly_sample(gf_ctx* ctx, const KnnPolyArgs& a);
-hipError_t launch_knn_poly_scan(gf_ctx* ctx, const KnnPolyArgs& a, int blocks);  // prefilter + refine
+// chain != 0: a linestring query (a.poly carries the chain: the CHAIN kernels' open-chain distance)
+hipError_t launch_knn_poly_sample(gf_ctx* ctx, const KnnPolyArgs& a, int chain);
+hipError_t launch_knn_poly_scan(gf_ctx* ctx, const KnnPolyArgs& a, int blocks, int chain);  // prefilter + refine
 struct KnnSelectArgs;
 struct KnnMergeArgs;
 // pipelined: prefilter of this window + (block 0) an earlier window's select / window merge, then refine
 hipError_t launch_knn_poly_fused(gf_ctx* ctx, const KnnPolyArgs& a, const KnnSelectArgs& prev, int has_prev,
-                                 int blocks, const KnnMergeArgs* merge);
+                                 int blocks, const KnnMergeArgs* merge, int chain);
 // k > kMaxK: the merge ranks every entry by binary searches in the other (sorted) records and
 // dedupes through a hash table, both in global scratch of merge_any_bytes(nrec, k) per window
 // (`scratch` may be null for k <= kMaxK)
@@ -939,6 +966,7 @@ int knn_enqueue_merge(gf_knn_plan* P, const gf_points* pts, void* result, const 
 // a window's select has not run yet (its record completes with a later launch or the flush)
 bool knn_select_pending(const gf_knn_plan* P);
 
+// poly: 0 query points, 1 polygons, 2 linestrings (the POLY template parameter of the range kernels)
 hipError_t launch_range(gf_ctx* ctx, const RangeArgs& a, int table_mode, int poly, int blocks);
 // a batch of windows of one plan in one launch (blockIdx.y = window; inline tests, DEFER 0)
 struct RangeWin {
@@ -968,7 +996,8 @@ struct RangeGatherArgs {
 };
 hipError_t launch_range_window_gather(hipStream_t s, const RangeGatherArgs& a);
 hipError_t launch_join_ppoly(gf_ctx* ctx, const RangeArgs& a, int blocks, int jblocks, uint32_t* ecnt, uint32_t* ecand,
-                             uint32_t* btot, unsigned long long* total, uint32_t* pairs, int64_t cap, int aligned);
+                             uint32_t* btot, unsigned long long* total, uint32_t* pairs, int64_t cap, int aligned,
+                             int poly);
 
 struct JoinArgs {
   const double* ox;
@@ -1185,6 +1214,11 @@ struct gf_range_plan {
   uint32_t* jecand = nullptr;      // [queue_cap * 4] their first polygon indices (kJoinKeep)
   uint32_t* jbtot = nullptr;       // [num_cus * 8] pairs per join block
   unsigned long long* jtotal = nullptr;
+  // linestring plans (gf_range_pls_plan_create, gf_join_pls_plan_create): poly == 2, one open chain per
+  // object (vert_off / vx / vy), no ring_off / ring_env / rect; the chains' runs and their envelopes
+  int chain_mode = 0;              // 0: sub-chain envelopes, 1: the plain segment loop
+  int32_t* run_off = nullptr;      // [npoly + 1]
+  double* run_env = nullptr;       // [runs * 4] x1, y1, x2, y2
 };
 
 struct gf_knn_plan {
@@ -1239,6 +1273,9 @@ struct gf_knn_plan {
   double bbox[4] = {0, 0, 0, 0};
   uint32_t* maybe_i[3] = {nullptr, nullptr, nullptr};  // one per stream (lane j uses j % S), cap entries
   int64_t maybe_cap = 0;
+  // linestring query (gf_knn_pls_plan_create): poly == 2, the open chain in vert_off / vx / vy, its runs
+  // of kChainRun segments in ring_off ({0, runs}) and their envelopes (x1, y1, x2, y2) in ring_env
+  int chain_mode = 0;              // 0: sub-chain envelopes, 1: the plain segment loop
 };
 
 struct gf_window {

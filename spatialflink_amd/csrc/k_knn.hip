@@ -1286,13 +1286,28 @@ hipError_t launch_knn_merge_list(gf_ctx* ctx, int32_t k, const KnnRecList& list,
 // T: the continuous-query hint or a 256K-point sample's k-th distance (as for point queries);
 // the candidates then go through the same select (dedupe by objID, (d, objID) order).
 // ---------------------------------------------------------------------------------------
+// CHAIN (a linestring query, PointLineStringKNNQuery.java windowBased -> KNNQuery's window-all
+// evaluation): the same candidates with d = the open-chain distance (gf_geom.hpp chain_distance, the
+// value kept: runs are skipped against min(md, T)), selected at compile time.  a.poly then carries the
+// chain (ring_off = its run offsets, ring_env = the run envelopes).
+template <int CHAIN>
+__device__ __forceinline__ double poly_exact_distance(const KnnPolyArgs& a, double px, double py, double T) {
+  if constexpr (CHAIN)
+    return chain_distance<true>(px, py, ChainView{a.poly.ring_off, a.poly.vert_off, a.poly.vx, a.poly.vy, a.poly.ring_env,
+                                                  a.poly.metric}, 0, T);
+  else
+    return polygon_distance(px, py, a.poly, 0);
+}
+
+template <int CHAIN>
 __device__ __forceinline__ bool poly_pass(const KnnPolyArgs& a, double px, double py, double T, double& d) {
   if (!classify_cg(a.qr, px, py)) return false;
   if (px == px && py == py && env_far(a.bbox, px, py, T)) return false;
-  d = a.approx ? point_bbox_distance(px, py, a.bbox) : polygon_distance(px, py, a.poly, 0);
+  d = a.approx ? point_bbox_distance(px, py, a.bbox) : poly_exact_distance<CHAIN>(a, px, py, T);
   return d <= T;
 }
 
+template <int CHAIN>
 __global__ __launch_bounds__(kBlock) void knn_poly_sample_kernel(KnnPolyArgs a) {
   __shared__ uint32_t lh[kDistBins];
   if (a.use_hint) {
@@ -1311,7 +1326,7 @@ __global__ __launch_bounds__(kBlock) void knn_poly_sample_kernel(KnnPolyArgs a) 
   for (int u = threadIdx.x; u < kSamplePerBlock; u += kBlock) {
     const double px = a.x[p0 + u], py = a.y[p0 + u];
     double d;
-    if (poly_pass(a, px, py, a.r, d)) atomicAdd(&lh[dist_bin(d, bbase)], 1u);
+    if (poly_pass<CHAIN>(a, px, py, a.r, d)) atomicAdd(&lh[dist_bin(d, bbase)], 1u);
   }
   sample_finish(a.st, lh, a.k, a.r, a.poly.metric, bbase);
 }
@@ -1383,6 +1398,7 @@ __global__ __launch_bounds__(kBlock) void knn_poly_fused_kernel(KnnPolyArgs a, K
 
 // Refine: exact distance of each prefilter survivor; d <= T -> (d, idx, objID) candidates.  A
 // maybe-list past capacity marks the window overflowed (count > cap) for the select.
+template <int CHAIN>
 __global__ __launch_bounds__(kBlock) void knn_poly_refine_kernel(KnnPolyArgs a) {
   const double T = a.use_state ? a.st->T : a.r;
   const unsigned long long nm = a.st->maybe;
@@ -1399,7 +1415,7 @@ __global__ __launch_bounds__(kBlock) void knn_poly_refine_kernel(KnnPolyArgs a) 
     bool c = false;
     if (in) {
       const double px = a.x[i], py = a.y[i];
-      d = a.approx ? point_bbox_distance(px, py, a.bbox) : polygon_distance(px, py, a.poly, 0);
+      d = a.approx ? point_bbox_distance(px, py, a.bbox) : poly_exact_distance<CHAIN>(a, px, py, T);
       c = d <= T;
     }
     wave_reserve(&a.st->count, c, [&a, d, i](unsigned long long pos) {
@@ -1412,14 +1428,20 @@ __global__ __launch_bounds__(kBlock) void knn_poly_refine_kernel(KnnPolyArgs a) 
   }
 }
 
-hipError_t launch_knn_poly_sample(gf_ctx* ctx, const KnnPolyArgs& a) {
+hipError_t launch_knn_poly_sample(gf_ctx* ctx, const KnnPolyArgs& a, int chain) {
   KTimer t(ctx, GF_K_KNN_SAMPLE);
-  hipLaunchKernelGGL(knn_poly_sample_kernel, dim3(kSampleBlocks), dim3(kBlock), 0, ctx->stream, a);
+  if (chain) hipLaunchKernelGGL(knn_poly_sample_kernel<1>, dim3(kSampleBlocks), dim3(kBlock), 0, ctx->stream, a);
+  else hipLaunchKernelGGL(knn_poly_sample_kernel<0>, dim3(kSampleBlocks), dim3(kBlock), 0, ctx->stream, a);
   return hipGetLastError();
 }
 
+static void launch_knn_poly_refine(gf_ctx* ctx, const KnnPolyArgs& a, int chain) {
+  if (chain) hipLaunchKernelGGL(knn_poly_refine_kernel<1>, dim3(256), dim3(kBlock), 0, ctx->stream, a);
+  else hipLaunchKernelGGL(knn_poly_refine_kernel<0>, dim3(256), dim3(kBlock), 0, ctx->stream, a);
+}
+
 hipError_t launch_knn_poly_fused(gf_ctx* ctx, const KnnPolyArgs& a, const KnnSelectArgs& prev, int has_prev,
-                                 int blocks, const KnnMergeArgs* merge) {
+                                 int blocks, const KnnMergeArgs* merge, int chain) {
   KnnMergeArgs m{};
   if (merge && has_prev) m = *merge;
   {
@@ -1428,16 +1450,16 @@ hipError_t launch_knn_poly_fused(gf_ctx* ctx, const KnnPolyArgs& a, const KnnSel
   }
   KnnPolyArgs r = a;
   r.use_state = 1;  // the refine reads the threshold the scan blocks stored
-  hipLaunchKernelGGL(knn_poly_refine_kernel, dim3(256), dim3(kBlock), 0, ctx->stream, r);
+  launch_knn_poly_refine(ctx, r, chain);
   return hipGetLastError();
 }
 
-hipError_t launch_knn_poly_scan(gf_ctx* ctx, const KnnPolyArgs& a, int blocks) {
+hipError_t launch_knn_poly_scan(gf_ctx* ctx, const KnnPolyArgs& a, int blocks, int chain) {
   {
     KTimer t(ctx, GF_K_KNN_SCAN);
     hipLaunchKernelGGL(knn_poly_scan_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, a);
   }
-  hipLaunchKernelGGL(knn_poly_refine_kernel, dim3(256), dim3(kBlock), 0, ctx->stream, a);
+  launch_knn_poly_refine(ctx, a, chain);
   return hipGetLastError();
 }
 

@@ -27,9 +27,15 @@
 
 namespace gf {
 
-// DistanceOp(point, polygon) of polygon p of the plan's set (gf_geom.hpp)
+// DistanceOp(point, polygon) of polygon p of the plan's set (gf_geom.hpp).  POLY == 2, a linestring
+// plan (PointLineStringRangeQuery.java:100-172, PointLineStringJoinQuery.java): the open-chain distance
+// of line p instead, selected at compile time; only d <= r is asked of it here (bound r).
+template <int POLY>
 __device__ __forceinline__ double point_polygon_distance(double px, double py, const RangeArgs& a, int p) {
-  return polygon_distance(px, py, PolyView{a.ring_off, a.vert_off, a.vx, a.vy, a.ring_env, a.metric, a.rect}, p);
+  if constexpr (POLY == 2)
+    return chain_distance<false>(px, py, ChainView{a.ring_off, a.vert_off, a.vx, a.vy, a.ring_env, a.metric}, p, a.r);
+  else
+    return polygon_distance(px, py, PolyView{a.ring_off, a.vert_off, a.vx, a.vy, a.ring_env, a.metric, a.rect}, p);
 }
 
 // ---------------- classification --------------------------------------------------------
@@ -175,14 +181,14 @@ __device__ __forceinline__ bool test_point(const RangeArgs& a, double px, double
   if (finite) {
     for (int32_t t = b; t < e; ++t) {  // pass 1: envelopes holding the point (usually a hit)
       const int32_t o = lst ? lst[t] : t;
-      if (env_holds(a.bbox + 4 * o, px, py) && point_polygon_distance(px, py, a, o) <= a.r) return true;
+      if (env_holds(a.bbox + 4 * o, px, py) && point_polygon_distance<POLY>(px, py, a, o) <= a.r) return true;
     }
   }
   for (int32_t t = b; t < e; ++t) {  // pass 2: the rest, envelope-pruned
     const int32_t o = lst ? lst[t] : t;
     const double* bb = a.bbox + 4 * o;
     if (finite && (env_holds(bb, px, py) || env_far(bb, px, py, a.r))) continue;
-    if (point_polygon_distance(px, py, a, o) <= a.r) return true;
+    if (point_polygon_distance<POLY>(px, py, a, o) <= a.r) return true;
   }
   return false;
 }
@@ -564,7 +570,7 @@ __device__ __forceinline__ bool test_object(const RangeArgs& a, double px, doubl
   }
   if (a.approx) return point_bbox_distance(px, py, a.bbox + 4 * o) <= a.r;
   if (px == px && py == py && env_far(a.bbox + 4 * o, px, py, a.r)) return false;
-  return point_polygon_distance(px, py, a, o) <= a.r;
+  return point_polygon_distance<POLY>(px, py, a, o) <= a.r;
 }
 
 #ifndef GF_RANGE_TEST_GROUP
@@ -851,7 +857,7 @@ __device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t* total,
 }
 
 // the polygons of (px, py)'s list that pair with it, in list order: sink(rank, q)
-template <class Sink>
+template <int POLY, class Sink>
 __device__ __forceinline__ uint32_t join_ppoly_walk(const RangeArgs& a, double px, double py, Sink&& sink) {
   const int32_t cx = cell_index(px, a.minX, a.cl), cy = cell_index(py, a.minY, a.cl);
   int32_t lb = 0, le = a.npoly;
@@ -878,7 +884,7 @@ __device__ __forceinline__ uint32_t join_ppoly_walk(const RangeArgs& a, double p
       const int64_t c = a.c_layers;
       key = key || (c > 0 && cx >= 0 && cy >= 0 && cx < a.grid_n && cy < a.grid_n && (int64_t)cx >= (int64_t)b.x - c &&
                     (int64_t)cx <= (int64_t)b.y + c && (int64_t)cy >= (int64_t)b.z - c && (int64_t)cy <= (int64_t)b.w + c);
-      if (key && (a.approx || test_object<1>(a, px, py, q[u]))) sink(n++, q[u]);
+      if (key && (a.approx || test_object<POLY>(a, px, py, q[u]))) sink(n++, q[u]);
     }
   }
   return n;
@@ -887,6 +893,7 @@ __device__ __forceinline__ uint32_t join_ppoly_walk(const RangeArgs& a, double p
 // Write pass: block offset = sum of the earlier blocks' counts (count pass), a block scan per
 // round of kBlock queued points, then the kept pairs are stored (a point with more than
 // kJoinKeep pairs walks its list again).
+template <int POLY>
 __global__ __launch_bounds__(kBlock) void join_ppoly_write_kernel(RangeArgs a, JoinPolyOut o) {
   __shared__ uint32_t ws[kBlock / 64];
   __shared__ unsigned long long part[kBlock / 64];
@@ -921,7 +928,7 @@ __global__ __launch_bounds__(kBlock) void join_ppoly_write_kernel(RangeArgs a, J
     if (c <= (uint32_t)kJoinKeep) {
       for (uint32_t k = 0; k < c; ++k) put(k, (int32_t)o.ecand[pos * kJoinKeep + k]);
     } else {
-      join_ppoly_walk(a, a.queue_xy[2 * pos], a.queue_xy[2 * pos + 1], put);
+      join_ppoly_walk<POLY>(a, a.queue_xy[2 * pos], a.queue_xy[2 * pos + 1], put);
     }
   }
 }
@@ -933,7 +940,10 @@ __global__ __launch_bounds__(kBlock) void join_ppoly_write_kernel(RangeArgs a, J
 // distance calls once per lane that needs one).  A point whose pairs overflow the worklist is
 // recounted by its own full walk.  Ranks inside a point come from LDS atomics (pair order is
 // unspecified); the set equals join_ppoly_walk's.
+// POLY == 2 (a linestring join plan, PointLineStringJoinQuery.java windowBased): no rectangle shells, the
+// open-chain distance in phase B.
 constexpr int kJoinWork = 4 * kBlock;  // worklist entries per round
+template <int POLY>
 __global__ __launch_bounds__(kBlock) void join_ppoly_count_kernel(RangeArgs a, JoinPolyOut o) {
   __shared__ uint32_t ws[kBlock / 64];
   __shared__ uint32_t pcnt[kBlock];
@@ -991,7 +1001,7 @@ __global__ __launch_bounds__(kBlock) void join_ppoly_count_kernel(RangeArgs a, J
             const double* bb = a.bbox + 4 * q[u];
             if (finite && env_far(bb, px, py, a.r)) continue;
             // rectangle shell: inside the closed box <=> distance 0 (<= r: keys exist only for r > 0)
-            hit = a.rect && a.rect[q[u]] && env_holds(bb, px, py);
+            if constexpr (POLY == 1) hit = a.rect && a.rect[q[u]] && env_holds(bb, px, py);
           }
           if (hit) {
             if (n < (uint32_t)kJoinKeep) o.ecand[pos * kJoinKeep + n] = (uint32_t)q[u];
@@ -1013,7 +1023,7 @@ __global__ __launch_bounds__(kBlock) void join_ppoly_count_kernel(RangeArgs a, J
       if (slow[sl]) continue;
       const double2 v = pxy[sl];
       const int32_t q = wl_poly[w];
-      if (point_polygon_distance(v.x, v.y, a, q) <= a.r) {
+      if (point_polygon_distance<POLY>(v.x, v.y, a, q) <= a.r) {
         const uint32_t rk = atomicAdd(&pcnt[sl], 1u);
         if (rk < (uint32_t)kJoinKeep) o.ecand[(base + i0 + sl) * kJoinKeep + rk] = (uint32_t)q;
       }
@@ -1021,7 +1031,7 @@ __global__ __launch_bounds__(kBlock) void join_ppoly_count_kernel(RangeArgs a, J
     __syncthreads();
     uint32_t total = pcnt[threadIdx.x];
     if (over)  // worklist overflow: this point's own full walk
-      total = join_ppoly_walk(a, px, py, [&](uint32_t k, int32_t q) {
+      total = join_ppoly_walk<POLY>(a, px, py, [&](uint32_t k, int32_t q) {
         if (k < (uint32_t)kJoinKeep) o.ecand[pos * kJoinKeep + k] = (uint32_t)q;
       });
     if (valid) {
@@ -1042,21 +1052,28 @@ __global__ __launch_bounds__(kBlock) void join_ppoly_count_kernel(RangeArgs a, J
 }
 
 hipError_t launch_join_ppoly(gf_ctx* ctx, const RangeArgs& a, int blocks, int jblocks, uint32_t* ecnt, uint32_t* ecand,
-                             uint32_t* btot, unsigned long long* total, uint32_t* pairs, int64_t cap, int aligned) {
+                             uint32_t* btot, unsigned long long* total, uint32_t* pairs, int64_t cap, int aligned,
+                             int poly) {
   const size_t lds = 4 * kRangeHdrWords + sizeof(uint32_t) * (size_t)((2 * a.grid_n + 1) & ~1) +
                      (a.xt ? 2 * sizeof(double) * (size_t)(a.grid_n + 1) : 0) +
                      (a.span_lds ? (size_t)((a.span_bytes + 3) & ~3) : 0);
   {
     KTimer t(ctx, GF_K_RANGE_SCAN);
-    hipLaunchKernelGGL((range_kernel<1, 1, 2, kRangeU>), dim3(blocks), dim3(kBlock), lds, ctx->stream, a);
+    if (poly == 2) hipLaunchKernelGGL((range_kernel<1, 2, 2, kRangeU>), dim3(blocks), dim3(kBlock), lds, ctx->stream, a);
+    else hipLaunchKernelGGL((range_kernel<1, 1, 2, kRangeU>), dim3(blocks), dim3(kBlock), lds, ctx->stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   KTimer t(ctx, GF_K_RANGE_TEST);
   JoinPolyOut o{ecnt, ecand, btot, total, pairs, cap, aligned};
   (void)jblocks;  // one block per scan block's queue segment
-  hipLaunchKernelGGL(join_ppoly_count_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, a, o);
-  hipLaunchKernelGGL(join_ppoly_write_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, a, o);
+  if (poly == 2) {
+    hipLaunchKernelGGL(join_ppoly_count_kernel<2>, dim3(blocks), dim3(kBlock), 0, ctx->stream, a, o);
+    hipLaunchKernelGGL(join_ppoly_write_kernel<2>, dim3(blocks), dim3(kBlock), 0, ctx->stream, a, o);
+  } else {
+    hipLaunchKernelGGL(join_ppoly_count_kernel<1>, dim3(blocks), dim3(kBlock), 0, ctx->stream, a, o);
+    hipLaunchKernelGGL(join_ppoly_write_kernel<1>, dim3(blocks), dim3(kBlock), 0, ctx->stream, a, o);
+  }
   return hipGetLastError();
 }
 
@@ -1075,6 +1092,10 @@ hipError_t launch_range(gf_ctx* ctx, const RangeArgs& a, int table_mode, int pol
       if (defer && a.span_mode) hipLaunchKernelGGL((range_kernel<1, 0, 3, kRangeU>), g, b, lds, ctx->stream, a);
       else if (defer) hipLaunchKernelGGL((range_kernel<1, 0, 1, kRangeU>), g, b, lds, ctx->stream, a);
       else hipLaunchKernelGGL((range_kernel<1, 0, 0, kRangeU>), g, b, lds, ctx->stream, a);
+    } else if (poly == 2) {  // linestring plans
+      if (defer && a.span_mode) hipLaunchKernelGGL((range_kernel<1, 2, 3, kRangeU>), g, b, lds, ctx->stream, a);
+      else if (defer) hipLaunchKernelGGL((range_kernel<1, 2, 1, kRangeU>), g, b, lds, ctx->stream, a);
+      else hipLaunchKernelGGL((range_kernel<1, 2, 0, kRangeU>), g, b, lds, ctx->stream, a);
     } else {
       if (defer && a.span_mode) hipLaunchKernelGGL((range_kernel<1, 1, 3, kRangeU>), g, b, lds, ctx->stream, a);
       else if (defer) hipLaunchKernelGGL((range_kernel<1, 1, 1, kRangeU>), g, b, lds, ctx->stream, a);
@@ -1096,6 +1117,7 @@ hipError_t launch_range_batch(gf_ctx* ctx, const RangeArgs& a, const RangeBatch&
   KTimer k(ctx, GF_K_RANGE_SCAN);
   if (!table_mode && !poly) hipLaunchKernelGGL((range_batch_kernel<0, 0, kRangeU>), g, t, lds, ctx->stream, a, b);
   else if (!poly) hipLaunchKernelGGL((range_batch_kernel<1, 0, kRangeU>), g, t, lds, ctx->stream, a, b);
+  else if (poly == 2) hipLaunchKernelGGL((range_batch_kernel<1, 2, kRangeU>), g, t, lds, ctx->stream, a, b);
   else hipLaunchKernelGGL((range_batch_kernel<1, 1, kRangeU>), g, t, lds, ctx->stream, a, b);
   return hipGetLastError();
 }

@@ -11,6 +11,7 @@
 #include <limits>
 #include <unordered_set>
 
+#include "gf_chain_plan.hpp"
 #include "gf_host.hpp"
 
 using namespace gf;
@@ -97,6 +98,37 @@ extern "C" int gf_knn_pp_plan_create(gf_ctx* ctx, const gf_grid* g, double qx, d
   return GF_OK;
 }
 
+// C u G of the cells under P->bbox (x1, y1, x2, y2) as one rect pair: valid cells within c of the bbox
+// rect; for g == 0 the bbox cells themselves, no validKey.  Shared by the polygon and the linestring
+// query (UniformGrid.java:193-222, 399-426: per-bbox-cell unions in both forms).
+static void bbox_query_rect(gf_knn_plan* P, const gf_grid* g, double r) {
+  const int32_t gl = guaranteed_layers(g->cellLength, r), cl = candidate_layers(g->cellLength, r);
+  const int64_t bx0 = cell_index(P->bbox[0], g->minX, g->cellLength), bx1 = cell_index(P->bbox[2], g->minX, g->cellLength);
+  const int64_t by0 = cell_index(P->bbox[1], g->minY, g->cellLength), by1 = cell_index(P->bbox[3], g->minY, g->cellLength);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  const int64_t n1 = g->n - 1;
+  QueryRect q;
+  q.minX = g->minX;
+  q.minY = g->minY;
+  if (cl > 0) {
+    q.cgx = axis_iv(std::max<int64_t>(bx0 - cl, 0), std::min<int64_t>(bx1 + cl, n1), g->minX, g->cellLength);
+    q.cgy = axis_iv(std::max<int64_t>(by0 - cl, 0), std::min<int64_t>(by1 + cl, n1), g->minY, g->cellLength);
+  } else {
+    q.cgx = q.cgy = {nan, nan};
+  }
+  if (gl > 0) {
+    q.gx = axis_iv(std::max<int64_t>(bx0 - gl, 0), std::min<int64_t>(bx1 + gl, n1), g->minX, g->cellLength);
+    q.gy = axis_iv(std::max<int64_t>(by0 - gl, 0), std::min<int64_t>(by1 + gl, n1), g->minY, g->cellLength);
+  } else if (gl == 0) {  // the bbox cells themselves, without validKey
+    q.gx = axis_iv(bx0, bx1, g->minX, g->cellLength);
+    q.gy = axis_iv(by0, by1, g->minY, g->cellLength);
+  } else {
+    q.gx = q.gy = {nan, nan};
+  }
+  q.g_any = (gl >= 0) && !std::isnan(q.gx.lo) && !std::isnan(q.gy.lo);
+  P->qr = q;
+}
+
 // PointPolygonKNNQuery.run(stream, queryPolygon, r, k) -- knn/PointPolygonKNNQuery.java:245-317:
 // the C u G cells of the polygon's bbox cells (UniformGrid.java:193-206,399-411) as one rect
 // pair (valid cells within c of the bbox rect; for g == 0 the bbox cells themselves, no
@@ -130,31 +162,7 @@ extern "C" int gf_knn_ppoly_plan_create(gf_ctx* ctx, const gf_grid* g, const gf_
     renv[4 * j] = mnx; renv[4 * j + 1] = mxx; renv[4 * j + 2] = mny; renv[4 * j + 3] = mxy;
   }
   P->bbox[0] = renv[0]; P->bbox[1] = renv[2]; P->bbox[2] = renv[1]; P->bbox[3] = renv[3];  // shell envelope
-  const int32_t gl = guaranteed_layers(g->cellLength, r), cl = candidate_layers(g->cellLength, r);
-  const int64_t bx0 = cell_index(P->bbox[0], g->minX, g->cellLength), bx1 = cell_index(P->bbox[2], g->minX, g->cellLength);
-  const int64_t by0 = cell_index(P->bbox[1], g->minY, g->cellLength), by1 = cell_index(P->bbox[3], g->minY, g->cellLength);
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  const int64_t n1 = g->n - 1;
-  QueryRect q;
-  q.minX = g->minX;
-  q.minY = g->minY;
-  if (cl > 0) {
-    q.cgx = axis_iv(std::max<int64_t>(bx0 - cl, 0), std::min<int64_t>(bx1 + cl, n1), g->minX, g->cellLength);
-    q.cgy = axis_iv(std::max<int64_t>(by0 - cl, 0), std::min<int64_t>(by1 + cl, n1), g->minY, g->cellLength);
-  } else {
-    q.cgx = q.cgy = {nan, nan};
-  }
-  if (gl > 0) {
-    q.gx = axis_iv(std::max<int64_t>(bx0 - gl, 0), std::min<int64_t>(bx1 + gl, n1), g->minX, g->cellLength);
-    q.gy = axis_iv(std::max<int64_t>(by0 - gl, 0), std::min<int64_t>(by1 + gl, n1), g->minY, g->cellLength);
-  } else if (gl == 0) {  // the bbox cells themselves, without validKey
-    q.gx = axis_iv(bx0, bx1, g->minX, g->cellLength);
-    q.gy = axis_iv(by0, by1, g->minY, g->cellLength);
-  } else {
-    q.gx = q.gy = {nan, nan};
-  }
-  q.g_any = (gl >= 0) && !std::isnan(q.gx.lo) && !std::isnan(q.gy.lo);
-  P->qr = q;
+  bbox_query_rect(P, g, r);
   const int32_t nverts = poly->vert_off[nrings];
   std::vector<int32_t> ro = {0, nrings}, vo(poly->vert_off, poly->vert_off + nrings + 1);
   std::vector<double> vx(poly->vx, poly->vx + nverts), vy(poly->vy, poly->vy + nverts);
@@ -164,6 +172,41 @@ extern "C" int gf_knn_ppoly_plan_create(gf_ctx* ctx, const gf_grid* g, const gf_
     return st;
   }
   *out = P;
+  return GF_OK;
+}
+
+// PointLineStringKNNQuery.run(stream, queryLineString, r, k) -- knn/PointLineStringKNNQuery.java
+// windowBased: the polygon query with the geometry renamed (C u G of the line's bbox cells, the bbox
+// distance when approximate) and the open-chain distance (DistanceFunctions.java:38-42) when exact.
+// poly == 2; the plan's ring fields carry the chain's runs of kChainRun segments and their envelopes.
+extern "C" int gf_knn_pls_plan_create(gf_ctx* ctx, const gf_grid* g, const gf_linestrings* lines, double r,
+                                      int32_t k, int approximate, int metric, gf_knn_plan** out) {
+  if (!ctx || !out || !grid_ok(g) || !chain_valid(lines) || lines->nline != 1 || k < 1 || k > kMaxKLarge ||
+      (metric != 0 && metric != 1))
+    return set_err(ctx, GF_ERR_ARG, "gf_knn_pls_plan_create: bad argument (one line of >= 2 vertices, 1 <= k <= 2^24)");
+  *out = nullptr;
+  int st = gf_knn_pp_plan_create(ctx, g, 0.0, 0.0, r, k, metric, out);
+  if (st) return st;
+  gf_knn_plan* P = *out;
+  *out = nullptr;
+  P->poly = 2;
+  P->approx = approximate != 0;
+  ChainTables T;
+  chain_build(*lines, kChainRun, T);
+  for (int i = 0; i < 4; ++i) P->bbox[i] = T.bbox[i];
+  bbox_query_rect(P, g, r);
+  if ((st = upload(ctx, &P->ring_off, T.run_off)) || (st = upload(ctx, &P->vert_off, T.vert_off)) ||
+      (st = upload(ctx, &P->vx, T.vx)) || (st = upload(ctx, &P->vy, T.vy)) || (st = upload(ctx, &P->ring_env, T.run_env))) {
+    gf_knn_plan_destroy(P);
+    return st;
+  }
+  *out = P;
+  return GF_OK;
+}
+
+extern "C" int gf_knn_plan_set_chain_mode(gf_knn_plan* P, int mode) {
+  if (!P || P->poly != 2 || (mode != 0 && mode != 1)) return GF_ERR_ARG;
+  P->chain_mode = mode;
   return GF_OK;
 }
 
@@ -226,6 +269,7 @@ static KnnPolyArgs poly_args(gf_knn_plan* P, int j, const gf_points* pts, int64_
   a.x = pts->x; a.y = pts->y; a.objID = pts->objID; a.begin = begin; a.end = end;
   a.qr = P->qr;
   a.poly = PolyView{P->ring_off, P->vert_off, P->vx, P->vy, P->ring_env, P->metric};
+  if (P->poly == 2 && P->chain_mode == 1) a.poly.ring_off = nullptr;  // linestring, mode 1: the plain segment loop
   for (int i = 0; i < 4; ++i) a.bbox[i] = P->bbox[i];
   a.approx = P->approx; a.r = P->r; a.k = P->k; a.use_state = use_state; a.use_hint = use_hint;
   a.st = L.st; a.cand_d = L.cand_d; a.cand_i = L.cand_i; a.cand_o = L.cand_o; a.cap = (unsigned long long)P->cap;
@@ -267,7 +311,7 @@ static int scan_blocks_for(gf_knn_plan* P, int64_t n) {
 // the window's threshold into the lane's state: its hint (use_hint, when it has one) or a sample
 static int launch_sample(gf_knn_plan* P, int j, const gf_points* pts, int use_hint) {
   if (P->poly) {
-    GF_HIP_CHECK(P->ctx, launch_knn_poly_sample(P->ctx, poly_args(P, j, pts, 0, pts->n, 1, use_hint)));
+    GF_HIP_CHECK(P->ctx, launch_knn_poly_sample(P->ctx, poly_args(P, j, pts, 0, pts->n, 1, use_hint), P->poly == 2));
     return GF_OK;
   }
   KnnSampleArgs s{};
@@ -284,7 +328,7 @@ static int launch_scan(gf_knn_plan* P, int j, const gf_points* pts, int64_t begi
   const int blocks = scan_blocks_for(P, end - begin);
   if (P->poly) {
     if (int st = poly_buffers(P)) return st;
-    GF_HIP_CHECK(ctx, launch_knn_poly_scan(ctx, poly_args(P, j, pts, begin, end, use_state, 0), blocks));
+    GF_HIP_CHECK(ctx, launch_knn_poly_scan(ctx, poly_args(P, j, pts, begin, end, use_state, 0), blocks, P->poly == 2));
   } else {
     GF_HIP_CHECK(ctx, launch_knn_scan(ctx, scan_args(P, j, pts, begin, end, use_state), blocks, P->scan_unroll,
                                       P->scan_nt));
@@ -302,7 +346,7 @@ static int launch_fused(gf_knn_plan* P, int j, const gf_points* pts, int use_sta
   if (P->poly) {
     if (int st = poly_buffers(P)) return st;
     GF_HIP_CHECK(ctx, launch_knn_poly_fused(ctx, poly_args(P, j, pts, 0, pts->n, use_state, 0), prev, has_prev, blocks,
-                                           merge));
+                                           merge, P->poly == 2));
   } else {
     GF_HIP_CHECK(ctx, launch_knn_fused(ctx, scan_args(P, j, pts, 0, pts->n, use_state), prev, has_prev, blocks,
                                        P->scan_unroll, P->scan_nt, merge));

@@ -10,6 +10,7 @@
 #include <limits>
 #include <unordered_map>
 
+#include "gf_chain_plan.hpp"
 #include "gf_host.hpp"
 
 using namespace gf;
@@ -262,7 +263,7 @@ extern "C" void gf_range_plan_destroy(gf_range_plan* P) {
   void* bufs[] = {P->table, P->extra, P->cand_off, P->cand_list, P->qx, P->qy, P->ring_off, P->vert_off,
                   P->vx, P->vy, P->bbox, P->ring_env, P->partials, P->queue, P->queue_count, P->queue_xy, P->rows, P->xt, P->yt,
                   P->rowoff, P->spans, P->brect, P->rect, P->jecnt, P->jecand, P->jbtot, P->jtotal,
-                  P->batch_partials};
+                  P->batch_partials, P->run_off, P->run_env};
   for (void* b : bufs)
     if (b) hipFree(b);
   delete P;
@@ -413,6 +414,88 @@ int ppoly_plan_create(gf_ctx* ctx, const gf_grid* g, const gf_polygons* polys, d
 }
 }  // namespace
 
+namespace {
+// A linestring plan (PointLineStringRangeQuery.java:100-172; join != 0: PointLineStringJoinQuery.java's
+// replicated query side, JoinQuery.java:117-137) is a polygon plan with one "ring" per object and
+// poly == 2, which selects the open-chain distance in the kernels.  The polygon shortcuts that assume a
+// closed region are off: no rectangle detection (rect stays null), and in exact mode no inside cells --
+// a cell under a closed chain is still at its distance to the nearest segment, so every candidate cell
+// is tested.  In approximate mode the bbox distance is 0 inside the bbox for lines too, and the bboxes
+// of positive area mark inside cells as they do for polygons.  Base cells: the cells under the vertex
+// envelope (LineString.java: HelperClass.assignGridCellID(bbox)) -- a zero-width or zero-height
+// bbox has x1 == x2 or y1 == y2 and yields the one column / row of cells its ordinate lies in.
+int pls_plan_create(gf_ctx* ctx, const gf_grid* g, const gf_linestrings* lines, double r, int approximate, int metric,
+                    int join, gf_range_plan** out) {
+  if (!ctx || !out || !grid_ok(g) || !chain_valid(lines) || (metric != 0 && metric != 1))
+    return set_err(ctx, GF_ERR_ARG, join ? "gf_join_pls_plan_create: bad argument (lines of >= 2 vertices)"
+                                         : "gf_range_pls_plan_create: bad argument (lines of >= 2 vertices)");
+  *out = nullptr;
+  int st = bind(ctx);
+  if (st) return st;
+  const int32_t nl = lines->nline;
+  ChainTables T;
+  chain_build(*lines, kChainRun, T);
+  gf_range_plan* P = new gf_range_plan();
+  P->ctx = ctx;
+  P->grid = *g;
+  P->r = r;
+  P->approx = approximate != 0;
+  P->metric = metric;
+  P->poly = 2;
+  P->table_mode = 1;
+  P->npoly = nl;
+  P->nq = nl;
+  P->g_layers = guaranteed_layers(g->cellLength, r);
+  P->c_layers = candidate_layers(g->cellLength, r);
+  P->join = join;
+  std::vector<Rect> base(nl);
+  std::vector<std::array<double, 4>> inside;
+  for (int32_t l = 0; l < nl; ++l) {
+    const double x1 = T.bbox[4 * l], y1 = T.bbox[4 * l + 1], x2 = T.bbox[4 * l + 2], y2 = T.bbox[4 * l + 3];
+    base[l] = {cell_index(x1, g->minX, g->cellLength), cell_index(x2, g->minX, g->cellLength),
+               cell_index(y1, g->minY, g->cellLength), cell_index(y2, g->minY, g->cellLength)};
+    if (P->approx && x1 < x2 && y1 < y2) inside.push_back({x1, y1, x2, y2});
+  }
+  if ((st = build_table(P, base, true, join ? nullptr : &inside, join != 0))) { gf_range_plan_destroy(P); return st; }
+  if (join) {
+    std::vector<int32_t> br(4 * (size_t)std::max(nl, 1), 0);
+    auto cl32 = [](int64_t v) { return (int32_t)std::min<int64_t>(std::max<int64_t>(v, INT32_MIN), INT32_MAX); };
+    for (int32_t l = 0; l < nl; ++l) {
+      br[4 * l] = cl32(base[l].x0); br[4 * l + 1] = cl32(base[l].x1);
+      br[4 * l + 2] = cl32(base[l].y0); br[4 * l + 3] = cl32(base[l].y1);
+    }
+    if ((st = upload(ctx, &P->brect, br))) { gf_range_plan_destroy(P); return st; }
+    GF_HIP_CHECK(ctx, hipMalloc(&P->jbtot, sizeof(uint32_t) * (size_t)ctx->num_cus * 8));
+    GF_HIP_CHECK(ctx, hipMalloc(&P->jtotal, sizeof(unsigned long long)));
+  }
+  if ((st = upload(ctx, &P->vert_off, T.vert_off)) || (st = upload(ctx, &P->vx, T.vx)) || (st = upload(ctx, &P->vy, T.vy)) ||
+      (st = upload(ctx, &P->bbox, T.bbox)) || (st = upload(ctx, &P->run_off, T.run_off)) ||
+      (st = upload(ctx, &P->run_env, T.run_env))) {
+    gf_range_plan_destroy(P);
+    return st;
+  }
+  if ((st = finish_plan(P))) { gf_range_plan_destroy(P); return st; }
+  *out = P;
+  return GF_OK;
+}
+}  // namespace
+
+extern "C" int gf_range_pls_plan_create(gf_ctx* ctx, const gf_grid* g, const gf_linestrings* lines, double r,
+                                        int approximate, int metric, gf_range_plan** out) {
+  return pls_plan_create(ctx, g, lines, r, approximate, metric, 0, out);
+}
+
+extern "C" int gf_join_pls_plan_create(gf_ctx* ctx, const gf_grid* qgrid, const gf_linestrings* lines, double r,
+                                       int approximate, int metric, gf_range_plan** out) {
+  return pls_plan_create(ctx, qgrid, lines, r, approximate, metric, 1, out);
+}
+
+extern "C" int gf_range_plan_set_chain_mode(gf_range_plan* P, int mode) {
+  if (!P || P->poly != 2 || (mode != 0 && mode != 1)) return GF_ERR_ARG;
+  P->chain_mode = mode;
+  return GF_OK;
+}
+
 extern "C" int gf_range_ppoly_plan_create(gf_ctx* ctx, const gf_grid* g, const gf_polygons* polys, double r,
                                           int approximate, int metric, gf_range_plan** out) {
   return ppoly_plan_create(ctx, g, polys, r, approximate, metric, 0, out);
@@ -445,6 +528,10 @@ RangeArgs range_args(const gf_range_plan* P, const gf_points* pts, uint64_t* bit
   a.qx = P->qx; a.qy = P->qy;
   a.npoly = P->npoly; a.ring_off = P->ring_off; a.vert_off = P->vert_off; a.vx = P->vx; a.vy = P->vy;
   a.bbox = P->bbox; a.ring_env = P->ring_env; a.rect = P->rect;
+  if (P->poly == 2) {  // a linestring plan: the runs travel in the ring fields (ChainView); mode 1: no runs
+    a.ring_off = P->chain_mode == 1 ? nullptr : P->run_off;
+    a.ring_env = P->run_env;
+  }
   a.brect = P->brect; a.g_layers = P->g_layers; a.c_layers = P->c_layers;
   return a;
 }
@@ -600,7 +687,7 @@ extern "C" int gf_join_ppoly_run(gf_range_plan* P, const gf_grid* ugrid, const g
   if ((st = ensure_queue(P, a, blocks, true))) return st;
   const int jblocks = blocks;  // one count/write block per scan block (its queue segment)
   GF_HIP_CHECK(ctx, launch_join_ppoly(ctx, a, blocks, jblocks, P->jecnt, P->jecand, P->jbtot, P->jtotal, pairs,
-                                      pairs ? cap : 0, pairs && ((uintptr_t)pairs % 8 == 0)));
+                                      pairs ? cap : 0, pairs && ((uintptr_t)pairs % 8 == 0), P->poly));
   unsigned long long total = 0;
   if ((st = read_scalar_sync(ctx, P->jtotal, &total))) return st;
   *npairs = (int64_t)total;
@@ -613,6 +700,17 @@ extern "C" int gf_join_ppoly(gf_ctx* ctx, const gf_grid* ugrid, const gf_grid* q
                              int64_t cap, int64_t* npairs) {
   gf_range_plan* P = nullptr;
   int st = gf_join_ppoly_plan_create(ctx, qgrid, polys, r, approximate, metric, &P);
+  if (st) return st;
+  st = gf_join_ppoly_run(P, ugrid, pts, pairs, cap, npairs);
+  gf_range_plan_destroy(P);
+  return st;
+}
+
+extern "C" int gf_join_pls(gf_ctx* ctx, const gf_grid* ugrid, const gf_grid* qgrid, const gf_points* pts,
+                           const gf_linestrings* lines, double r, int approximate, int metric, uint32_t* pairs,
+                           int64_t cap, int64_t* npairs) {
+  gf_range_plan* P = nullptr;
+  int st = gf_join_pls_plan_create(ctx, qgrid, lines, r, approximate, metric, &P);
   if (st) return st;
   st = gf_join_ppoly_run(P, ugrid, pts, pairs, cap, npairs);
   gf_range_plan_destroy(P);

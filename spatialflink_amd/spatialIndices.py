@@ -109,6 +109,8 @@ class UniformGrid:
 
     # -- neighbour-cell sets (UniformGrid.java:165-206, 261-293, 368-411)
     def _cells_of(self, query):
+        # a Polygon or a LineString carries the cells under its bbox (UniformGrid.java:193-222, 399-426: the
+        # polygon and linestring forms are the same per-bbox-cell unions), a Point or a cell id one cell
         gridIDsSet = getattr(query, "gridIDsSet", None)
         if gridIDsSet is not None:
             return list(gridIDsSet)

@@ -204,6 +204,66 @@ class PolygonSet:
         return h.digest()
 
 
+class LineString:
+    """LineString(String objID, List<Coordinate> coordinates, long timeStampMillisec, UniformGrid) --
+    LineString.java:103-113.  An open chain of >= 2 vertices (the reference's constructor leaves a null
+    JTS object for fewer and fails later; here a ValueError); repeated vertices and first == last are
+    legal and mean nothing special.  boundingBox is the vertex envelope (HelperClass.getBoundingBox),
+    gridIDsSet = every cell under the bbox (HelperClass.assignGridCellID(bBox) :123-143): a horizontal
+    or vertical line has a zero-height or zero-width bbox and still a row / column of cells."""
+
+    def __init__(self, coordinates, uGrid: Optional[UniformGrid] = None, objID=None, timeStampMillisec: int = 0):
+        coords = [(float(x), float(y)) for x, y in coordinates]
+        if len(coords) < 2:
+            raise ValueError("LineString needs 2 or more coordinates (LineString.java:104)")
+        self.coordinates = coords
+        self.objID = objID
+        self.timeStampMillisec = int(timeStampMillisec)
+        sx = [v[0] for v in coords]
+        sy = [v[1] for v in coords]
+        self.boundingBox = ((min(sx), min(sy)), (max(sx), max(sy)))
+        self.gridID = ""
+        self.gridIDsSet = set()
+        if uGrid is not None:
+            (x1, y1), (x2, y2) = self.boundingBox
+            a1, b1 = uGrid.cellOf(x1, y1)
+            a2, b2 = uGrid.cellOf(x2, y2)
+            self.gridIDsSet = {generateCellIDStr(a, b) for a in range(a1, a2 + 1) for b in range(b1, b2 + 1)}
+
+    def __repr__(self):
+        return f"LineString(vertices={len(self.coordinates)}, bbox={self.boundingBox})"
+
+
+class LineStringSet:
+    """Host CSR of a linestring set for the C ABI (gf_linestrings)."""
+
+    def __init__(self, lineStrings):
+        self.lineStrings = list(lineStrings)
+        vert_off, vx, vy = [0], [], []
+        for ls in self.lineStrings:
+            vx += [v[0] for v in ls.coordinates]
+            vy += [v[1] for v in ls.coordinates]
+            vert_off.append(len(vx))
+        self.vert_off = np.asarray(vert_off, np.int32)
+        self.vx = np.asarray(vx, np.float64)
+        self.vy = np.asarray(vy, np.float64)
+
+    def c_struct(self) -> _lib.GfLineStrings:
+        return _lib.GfLineStrings(len(self.lineStrings), self.vert_off.ctypes.data, self.vx.ctypes.data,
+                                  self.vy.ctypes.data)
+
+    def digest(self) -> bytes:
+        """Content key of the set (line layout + every vertex bit pattern), as PolygonSet.digest."""
+        import hashlib
+
+        h = hashlib.blake2b(digest_size=20)
+        h.update(b"linestrings")
+        for a in (self.vert_off, self.vx, self.vy):
+            h.update(np.int64(a.size).tobytes())
+            h.update(np.ascontiguousarray(a).tobytes())
+        return h.digest()
+
+
 @dataclass
 class PointWindow:
     """One window's points as device SoA (torch CUDA tensors)."""

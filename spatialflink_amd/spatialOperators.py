@@ -9,6 +9,9 @@ evaluates that window on the GPU through the C ABI -- the body of apply() is wha
   PointPointKNNQuery.run(window, Point, r, k)         -- knn/PointPointKNNQuery.java:33,132-201
   PointPointJoinQuery.run(ordinary, query, r)         -- join/PointPointJoinQuery.java:24,124-183
   PointPolygonJoinQuery.run(points, polygons, r)      -- join/PointPolygonJoinQuery.java:154-213
+  PointLineStringRangeQuery.run(window, Set<LineString>, r) -- range/PointLineStringRangeQuery.java:100-172
+  PointLineStringKNNQuery.run(window, LineString, r, k)     -- knn/PointLineStringKNNQuery.java (windowBased)
+  PointLineStringJoinQuery.run(points, lineStrings, r)      -- join/PointLineStringJoinQuery.java (windowBased)
 
 Errors follow the reference: unsupported query types raise ValueError ("Not yet support",
 IllegalArgumentException), candidate layers <= 0 raise CandidateLayersError (System.exit(1)).
@@ -24,7 +27,7 @@ import numpy as np
 
 from . import _lib
 from .spatialIndices import UniformGrid, generateCellIDStr
-from .spatialObjects import Point, PointWindow, Polygon, PolygonSet
+from .spatialObjects import LineString, LineStringSet, Point, PointWindow, Polygon, PolygonSet
 
 
 class QueryType(Enum):
@@ -312,6 +315,48 @@ class PointPolygonRangeQuery(_RangeBase):
         return ctx, self._plan(key, create)
 
 
+def _linestring_plan(op, create_name, grid, device, lineStrings, queryRadius):
+    """(context, plan, LineStringSet) of a linestring range / join plan of `op`, cached by the lines'
+    contents; op.chain_mode (testing / tuning: 1 = the plain segment loop) is part of the key."""
+    ls = lineStrings if isinstance(lineStrings, LineStringSet) else LineStringSet(lineStrings)
+    ctx = _lib.context(device)
+    mode = int(getattr(op, "chain_mode", 0))
+    key = (create_name, ctx.device, ls.digest(), float(queryRadius), bool(op.conf.approximateQuery),
+           int(op.conf.distanceMetric), mode)
+
+    def create():
+        cs = ls.c_struct()
+        h = C.c_void_p()
+        st = getattr(_lib.lib(), create_name)(ctx.handle, C.byref(grid.c_grid), C.byref(cs), float(queryRadius),
+                                              int(op.conf.approximateQuery), int(op.conf.distanceMetric), C.byref(h))
+        _lib.check(st, ctx.handle, create_name)
+        if mode:
+            _lib.check(_lib.lib().gf_range_plan_set_chain_mode(h, mode), ctx.handle, "gf_range_plan_set_chain_mode")
+        return h
+
+    return ctx, op._plan(key, create), ls
+
+
+class PointLineStringRangeQuery(_RangeBase):
+    """range/PointLineStringRangeQuery.java -- the point-polygon range query with the geometry renamed
+    (windowBased :100-172; realTime :35-97 is the same per-point predicate): a point of a guaranteed
+    cell is emitted, a point of a candidate cell if some line is within r -- Point.distance(LineString)
+    (DistanceFunctions.java:38-42, the minimum of pointToSegment over the open chain, no containment)
+    or, approximate, the bbox distance (:203-255)."""
+
+    def run(self, window: PointWindow, queryLineStringSet, queryRadius: float) -> RangeResult:
+        _require_supported(self.conf)
+        ctx, plan = self.plan(window.x.device.index, queryLineStringSet, queryRadius)
+        return self._evaluate(plan, window, 1)
+
+    def plan(self, device: int, queryLineStringSet, queryRadius: float):
+        """(context, gf_range_plan) of this query on `device` (cached by query contents)."""
+        _require_supported(self.conf)
+        ctx, plan, _ = _linestring_plan(self, "gf_range_pls_plan_create", self.index, device, queryLineStringSet,
+                                        queryRadius)
+        return ctx, plan
+
+
 # ----------------------------------------------------------------------------------------
 # kNN
 # ----------------------------------------------------------------------------------------
@@ -497,6 +542,36 @@ class PointPolygonKNNQuery(PointPointKNNQuery):
         return ctx, plan
 
 
+class PointLineStringKNNQuery(PointPointKNNQuery):
+    """knn/PointLineStringKNNQuery.java (windowBased, then KNNQuery.kNNWinAllEvaluationPointStream) --
+    continuous kNN of the window's points to one query linestring within r: candidates have their cell
+    in C u G of the line's bbox cells and d <= r, d = the open-chain distance (no containment) or,
+    approximate, the bbox distance.  The polygon query's record contract and run / enqueue / finish API
+    with a LineString as the query.  chain_mode = 1 (testing / tuning) runs the plain segment loop."""
+
+    chain_mode = 0
+
+    def plan(self, window_device: int, queryLineString: LineString, queryRadius: float, k: int):
+        ctx = _lib.context(window_device)
+        ls = LineStringSet([queryLineString])
+        mode = int(self.chain_mode)
+        key = (ctx.device, ls.digest(), float(queryRadius), int(k), int(self.conf.distanceMetric),
+               bool(self.conf.isApproximateQuery()), mode)
+        plan = self._plans.get(key)
+        if plan is None:
+            cs = ls.c_struct()
+            h = C.c_void_p()
+            st = _lib.lib().gf_knn_pls_plan_create(ctx.handle, C.byref(self.index.c_grid), C.byref(cs),
+                                                   float(queryRadius), int(k), int(self.conf.isApproximateQuery()),
+                                                   int(self.conf.distanceMetric), C.byref(h))
+            _lib.check(st, ctx.handle, "gf_knn_pls_plan_create")
+            if mode:
+                _lib.check(_lib.lib().gf_knn_plan_set_chain_mode(h, mode), ctx.handle, "gf_knn_plan_set_chain_mode")
+            self._plans.put(key, h)
+            plan = h
+        return ctx, plan
+
+
 def knn_merge_host(k: int, lists):
     """Top-k distinct objIDs of several sorted (objID, dist, idx) lists -- the windowAll funnel
     (KNNQuery.java:213-272) across shards; host code of the library (no GPU needed)."""
@@ -583,6 +658,43 @@ class PointPolygonJoinQuery(_RangeBase):
             return h
 
         plan = self._plan(key, create)
+        pts = pointWindow.c_struct()
+        cap = max(1024, 2 * pointWindow.n)
+        for _ in range(2):
+            pairs = torch.empty(2 * cap, dtype=torch.int32, device=pointWindow.x.device)
+            npairs = C.c_int64()
+            st = _lib.lib().gf_join_ppoly_run(plan, C.byref(self.index.c_grid), C.byref(pts), pairs.data_ptr(), cap,
+                                              C.byref(npairs))
+            if st == _lib.GF_ERR_CAPACITY:
+                cap = int(npairs.value)
+                continue
+            _lib.check(st, ctx.handle, "gf_join_ppoly_run")
+            m = int(npairs.value)
+            out = pairs[: 2 * m].cpu().numpy().view(np.uint32).astype(np.int64).reshape(-1, 2)
+            order = np.lexsort((out[:, 1], out[:, 0]))
+            return out[order]
+        raise _lib.GeoFlinkError(_lib.GF_ERR_CAPACITY, "join output kept growing")
+
+
+class PointLineStringJoinQuery(_RangeBase):
+    """join/PointLineStringJoinQuery.java (windowBased) -- window-based join of a point stream with a
+    linestring stream: line q is replicated to its own guaranteed + candidate cells
+    (JoinQuery.getReplicatedLineStringQueryStream, JoinQuery.java:117-137), point p pairs with q when
+    their cells match and either the query is approximate or the open-chain distance is <= r.  The
+    replicated side is a plan cached by the lines' contents, run by gf_join_ppoly_run; the device path
+    requires the two grids to be equal, as PointPolygonJoinQuery does."""
+
+    def __init__(self, conf: QueryConfiguration, index1: UniformGrid, index2: UniformGrid = None):
+        super().__init__(conf, index1)
+        self.index2 = index2 if index2 is not None else index1
+
+    def run(self, pointWindow: PointWindow, queryLineStrings, queryRadius: float) -> np.ndarray:
+        """Returns int64 [m, 2] pairs (point index, line index), sorted."""
+        import torch
+
+        _require_supported(self.conf)
+        ctx, plan, _ls = _linestring_plan(self, "gf_join_pls_plan_create", self.index2, pointWindow.x.device.index,
+                                          queryLineStrings, queryRadius)
         pts = pointWindow.c_struct()
         cap = max(1024, 2 * pointWindow.n)
         for _ in range(2):
@@ -1406,6 +1518,7 @@ class PointPointTJoinQuery:
 
 
 __all__ = [
+    "LineString", "LineStringSet", "PointLineStringRangeQuery", "PointLineStringKNNQuery", "PointLineStringJoinQuery",
     "PointPointTJoinQuery", "TJoinResult",
     "PointPolygonTRangeQuery", "PointTFilterQuery", "TRangePlan",
     "PointPointTKNNQuery", "TKNNResult",

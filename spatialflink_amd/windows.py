@@ -151,13 +151,15 @@ class SlidingKNNQuery:
     order)."""
 
     def __init__(self, conf: QueryConfiguration, grid, queryPoint: Point, queryRadius: float, k: int,
-                 size_ms: int = None, slide_ms: int = None, device: int = 0, pipeline: int = 2):
+                 size_ms: int = None, slide_ms: int = None, device: int = 0, pipeline: int = 2, op=None):
         _require_supported(conf)
         if k is None or int(k) < 1:
             raise ValueError("k must be >= 1 (PriorityQueue initialCapacity < 1)")
         self.geo = SlidingWindows(size_ms, slide_ms) if size_ms else SlidingWindows.from_conf(conf)
         self.k = int(k)
-        self.op = PointPointKNNQuery(conf, grid)
+        # op: another kNN operator whose plan the panes run on (PointPolygonKNNQuery, PointLineStringKNNQuery:
+        # queryPoint is then its query geometry); default the point query
+        self.op = op if op is not None else PointPointKNNQuery(conf, grid)
         self.ctx, self.plan = self.op.plan(device, queryPoint, queryRadius, k)
         self.op._plans.hold(self.plan)  # the pane engine borrows it
         self.depth = int(pipeline)  # k > 256: the select is not fused, records complete in stream order
