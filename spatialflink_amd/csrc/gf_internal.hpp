@@ -578,7 +578,11 @@ struct TrajGroupArgs {
   uint32_t ntraj;
   uint32_t* seg_off;        // [ntraj + 1]
 };
-// stage 0: clear + insert + flag; 1: assign + ids; 2: seg_off from the sorted ids
+enum TrajGroupStage {
+  kTrajGroupInsert = 0,  // clear + insert + flag
+  kTrajGroupAssign = 1,  // assign + ids
+  kTrajGroupBounds = 2,  // seg_off from the sorted ids
+};
 hipError_t launch_traj_group(gf_ctx* ctx, int stage, const TrajGroupArgs& a);
 struct TStatsArgs {
   const double* x;
@@ -595,7 +599,10 @@ struct TStatsArgs {
   uint32_t* long_count;     // zero before the launch
 };
 hipError_t launch_tstats(gf_ctx* ctx, const TStatsArgs& a);
-// stage 0: sel[t] = keys[t] in set (sorted, distinct); 1: the selected rows packed at rank[t]
+enum TStatsFilterStage {
+  kTStatsFilterMark = 0,  // sel[t] = keys[t] in set (sorted, distinct)
+  kTStatsFilterPack = 1,  // the selected rows packed at rank[t]
+};
 hipError_t launch_tstats_filter(gf_ctx* ctx, const TStatsArgs& a, const int64_t* keys, const int64_t* set, int64_t nset,
                                 uint32_t* sel, const uint32_t* rank, int64_t* ok, double* oS, int64_t* oT, double* oV,
                                 int stage);
@@ -610,7 +617,7 @@ struct TrajSelectArgs {
   const uint32_t* perm;
   const uint32_t* seg_off;
   const int64_t* keys;
-  uint32_t* hit;            // [ntraj + 1] zero before stage 0 (entry ntraj stays 0)
+  uint32_t* hit;            // [ntraj + 1] zero before kTrajSelectHit (entry ntraj stays 0)
   uint32_t* len;            // [ntraj + 1]
   const uint32_t* row;      // [ntraj + 1] scan of hit
   const uint32_t* off;      // [ntraj + 1] scan of len
@@ -621,14 +628,18 @@ struct TrajSelectArgs {
   int64_t* ots;
   uint32_t* oidx;
 };
-// stage 0: hit from the bitmap; 2: lens; 1: gather
+enum TrajSelectStage {  // issued as hit, lens, (the scans), gather
+  kTrajSelectHit = 0,     // hit from the bitmap
+  kTrajSelectGather = 1,
+  kTrajSelectLens = 2,
+};
 hipError_t launch_traj_select(gf_ctx* ctx, int stage, const TrajSelectArgs& a);
 
 // tAggregate (k_tagg.hip, tagg.cpp)
 constexpr int64_t kTaggLongLen = 2048;   // default: (cell, objID) groups of at least this many points take the block path
 constexpr int64_t kTaggBigCell = 1024;   // default: cells of at least this many groups take the block path
 struct TaggArgs {
-  // keys (stage 0 / 1)
+  // keys (kTaggCellKeys / kTaggPairKeys)
   const double* x;
   const double* y;
   int64_t n;
@@ -637,7 +648,7 @@ struct TaggArgs {
   const uint32_t* cid;      // [n] dense cell id per point
   const uint32_t* oid;      // [n] dense objID id per point
   int64_t* comp;            // [n] cid << 32 | oid
-  // per-group statistics (stage 2): group g = points perm[seg_off[g], seg_off[g + 1]) in window order
+  // per-group statistics (kTaggGroupStats): group g = points perm[seg_off[g], seg_off[g + 1]) in window order
   const int64_t* ts;
   const uint32_t* perm;
   const uint32_t* seg_off;
@@ -654,8 +665,8 @@ struct TaggArgs {
   uint32_t* g_f;            // [ngroups] window index at which L is first reached (m >= 2)
   uint32_t* g_s;            // [ngroups] window index of the second point (m >= 2)
   uint32_t* list;           // big cells
-  uint32_t* list_count;     // zero before the launch: stage 2 counts the long groups, stage 3 the listed cells
-  // per-cell aggregation (stage 3): cell c = groups gperm[cell_off[c], cell_off[c + 1])
+  uint32_t* list_count;     // zero before the launch: kTaggGroupStats counts the long groups, kTaggCells the listed cells
+  // per-cell aggregation (kTaggCells): cell c = groups gperm[cell_off[c], cell_off[c + 1])
   const uint32_t* gperm;
   const uint32_t* cell_off;
   const int64_t* ckeys;     // [ncells] pack(cx, cy) of a dense cell id
@@ -673,7 +684,12 @@ struct TaggArgs {
   int64_t* all_key;         // [ngroups] the ALL rows: objID key, length, in cell order
   int64_t* all_len;
 };
-// stage 0: cell keys; 1: composite keys; 2: per-group statistics; 3: per-cell aggregation + ALL rows
+enum TaggStage {
+  kTaggCellKeys = 0,
+  kTaggPairKeys = 1,    // the composite keys
+  kTaggGroupStats = 2,  // per-group statistics
+  kTaggCells = 3,       // per-cell aggregation + ALL rows
+};
 hipError_t launch_tagg(gf_ctx* ctx, int stage, const TaggArgs& a);
 
 // tKnn (k_tknn.hip, tknn.cpp)
@@ -681,7 +697,7 @@ constexpr int64_t kTknnBigCell = 512;  // default: cells of at least this many (
 constexpr unsigned long long kTknnNaN = 0x7FF8000000000000ull;  // Double.doubleToLongBits(NaN): above +inf as an integer
 constexpr unsigned long long kTknnNone = ~0ull;                 // no distance yet (above every distance)
 struct TknnArgs {
-  // scan (stage 0): the window's one pass
+  // scan (kTknnScanWindow): the window's one pass
   const double* x;
   const double* y;
   const uint32_t* did;      // [n] trajectory (dense objID id) per point
@@ -693,13 +709,13 @@ struct TknnArgs {
   uint32_t* e_t;            //   the trajectory,
   unsigned long long* e_d;  //   the distance's bits (NaN = kTknnNaN),
   uint32_t* e_i;            //   the window index
-  uint32_t* counters;       // zero before stage 0: [0] entries, [1] pairs of big cells, [2] records
-  // entries (stages 1, 2)
+  uint32_t* counters;       // zero before the scan: [0] entries, [1] pairs of big cells, [2] records
+  // entries (kTknnCompose, kTknnPairMin)
   int64_t m;
   const uint32_t* cid;      // [m] dense cell id per entry
   int64_t* comp;            // [m] cid << 32 | trajectory
   const uint32_t* pid;      // [m] dense pair id per entry
-  // pairs (stages 2 .. 5)
+  // pairs (kTknnPairMin .. kTknnCombine)
   int64_t npairs;
   const int64_t* pkeys;     // [npairs] the pairs' composite keys
   uint32_t* p_first;        // [npairs] smallest window index of the pair
@@ -712,7 +728,7 @@ struct TknnArgs {
   const uint32_t* sperm;    // pairs sorted by (cell id, d, trajectory) (big cells)
   uint32_t big_cell;
   int32_t k;
-  // trajectories (stages 5, 6)
+  // trajectories (kTknnCombine, kTknnSurvivors)
   int64_t ntraj;
   const uint32_t* seg_off;  // gf_traj_groups' segments: the size rule
   unsigned long long* tr_D; // [ntraj] D_t as bits (kTknnNone: in no list)
@@ -720,7 +736,7 @@ struct TknnArgs {
   uint32_t* surv;           // [ntraj] survivor flags
   const uint32_t* srank;    // [ntraj + 1] their scan
   uint32_t* slist;          // [survivors] the surviving trajectories, ascending
-  // result (stages 7, 8)
+  // result (kTknnRows, kTknnGather)
   int64_t rows, npts;
   const uint32_t* order;    // [survivors] survivor ranks by (D_t, t)
   const int64_t* tkeys;     // [ntraj] objID keys
@@ -737,8 +753,17 @@ struct TknnArgs {
   int64_t* o_ts;
   uint32_t* o_idx;
 };
-// stage 0 scan; 1 compose; 2 pair minima; 3 small cells' lists; 4 big cells' lists; 5 combine per
-// trajectory + survivor flags; 6 survivor list; 7 rows; 8 gather
+enum TknnStage {
+  kTknnScanWindow = 0,
+  kTknnCompose = 1,
+  kTknnPairMin = 2,    // pair minima
+  kTknnRankSmall = 3,  // small cells' lists
+  kTknnRankBig = 4,    // big cells' lists
+  kTknnCombine = 5,    // combine per trajectory + survivor flags
+  kTknnSurvivors = 6,  // survivor list
+  kTknnRows = 7,
+  kTknnGather = 8,
+};
 hipError_t launch_tknn(gf_ctx* ctx, int stage, const TknnArgs& a);
 // out[p] = (uint32)(src[index ? index[item] : item] >> shift), item = cur ? cur[p] : p: one 32-bit
 // word of a multi-word sort key, in the current order
@@ -826,9 +851,9 @@ struct TjoinArgs {
   uint32_t* o_tq;
   uint32_t* mark[2];        // [nt + 1] per side: trajectory owns an emitted row
   const uint32_t* mrank[2]; // [nt + 1] their scans
-  uint32_t* counters;       // [8] zero before the rows stage: [0] emitted rows; totals (stage 12): [1] ordinary
+  uint32_t* counters;       // [8] zero before the rows stage: [0] emitted rows; kTjoinTotals: [1] ordinary
                             // trajectories, [2] their points, [3] query trajectories, [4] their points
-  // CSR of one side (stages 11 .. 13)
+  // CSR of one side (kTjoinSideList .. kTjoinGather)
   int32_t side;
   int64_t nt;               // the side's trajectories
   uint32_t* tlist[2];       // [nt] emitted trajectories, ascending
@@ -841,9 +866,22 @@ struct TjoinArgs {
   int64_t* c_ts;
   uint32_t* c_idx;
 };
-// stage 0 query keys; 1 qrank + qord; 2 bucket-order arrays + run flags; 3 run starts + bucket offsets;
-// 4 run ends; 5 ordinary cell keys; 6 probe; 7 occupied flags; 8 compact; 9 rows + marks; 10 slots;
-// 11 one side's trajectory list; 12 totals; 13 one side's gather
+enum TjoinStage {  // issued in this order, but for kTjoinSideList (once per side) ahead of kTjoinRowSlots
+  kTjoinQueryKeys = 0,
+  kTjoinQueryRank = 1,     // qrank + qord
+  kTjoinQueryScatter = 2,  // bucket-order arrays + run flags
+  kTjoinRunStarts = 3,     // run starts + bucket offsets
+  kTjoinRunEnds = 4,
+  kTjoinCellKeys = 5,      // ordinary cell keys
+  kTjoinProbe = 6,
+  kTjoinOccupied = 7,      // occupied flags
+  kTjoinCompact = 8,
+  kTjoinRows = 9,          // rows + marks
+  kTjoinRowSlots = 10,
+  kTjoinSideList = 11,     // one side's trajectory list
+  kTjoinTotals = 12,
+  kTjoinGather = 13,       // one side's gather
+};
 hipError_t launch_tjoin(gf_ctx* ctx, int stage, const TjoinArgs& a);
 
 // tRange (k_trange.hip, trange.cpp)
@@ -868,7 +906,11 @@ struct TrangeArgs {
   unsigned long long* ctr;    // [0] worklist entries, [1] points in non-none cells, [2] in inside cells, [3] set bits
   int64_t* count;             // point mode, nullable: device, receives ctr[3]
 };
-// stage 0: the mark (one lane per point); 1: the wave path over the worklist; 2: the bitmap's count
+enum TrangeStage {
+  kTrangeMark = 0,   // one lane per point
+  kTrangeWaves = 1,  // the wave path over the worklist
+  kTrangeCount = 2,  // the bitmap's count
+};
 hipError_t launch_trange(gf_ctx* ctx, int stage, const TrangeArgs& a);
 
 hipError_t launch_knn_sample(gf_ctx* ctx, const KnnSampleArgs& a);

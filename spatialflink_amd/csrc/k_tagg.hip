@@ -311,19 +311,19 @@ hipError_t launch_tagg(gf_ctx* ctx, int stage, const TaggArgs& a) {
   KTimer timer(ctx, GF_K_TAGG);
   const dim3 blk(kBlock), wide((unsigned)ctx->num_cus * 4);
   switch (stage) {
-    case 0:
+    case kTaggCellKeys:
       hipLaunchKernelGGL(tagg_cellkey_kernel, dim3(tagg_blocks(ctx, (uint64_t)a.n)), blk, 0, s, a);
       break;
-    case 1:
+    case kTaggPairKeys:
       hipLaunchKernelGGL(tagg_compose_kernel, dim3(tagg_blocks(ctx, (uint64_t)a.n)), blk, 0, s, a);
       break;
-    case 2:
+    case kTaggGroupStats:
       hipLaunchKernelGGL(tagg_gstats_kernel, dim3(tagg_blocks(ctx, (uint64_t)a.ngroups)), blk, 0, s, a);
       hipLaunchKernelGGL(tagg_glong_kernel, dim3(tagg_blocks(ctx, (uint64_t)a.n)), blk, 0, s, a, 0);
       hipLaunchKernelGGL(tagg_glong_kernel, dim3(tagg_blocks(ctx, (uint64_t)a.n)), blk, 0, s, a, 1);
       hipLaunchKernelGGL(tagg_glong_rows_kernel, dim3(tagg_blocks(ctx, (uint64_t)a.ngroups)), blk, 0, s, a);
       break;
-    default:
+    default:  // kTaggCells
       hipLaunchKernelGGL(tagg_cell_kernel, dim3(tagg_blocks(ctx, (uint64_t)a.ncells)), blk, 0, s, a);
       hipLaunchKernelGGL(tagg_cbig_kernel, wide, blk, 0, s, a);
       hipLaunchKernelGGL(tagg_all_kernel, dim3(tagg_blocks(ctx, (uint64_t)a.ngroups)), blk, 0, s, a);

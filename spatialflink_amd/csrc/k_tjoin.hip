@@ -321,26 +321,26 @@ hipError_t launch_tjoin(gf_ctx* ctx, int stage, const TjoinArgs& a) {
   const dim3 gq(tjoin_blocks(ctx, (uint64_t)a.nq)), go(tjoin_blocks(ctx, (uint64_t)a.no)),
       gs(tjoin_blocks(ctx, (uint64_t)a.slots)), gr(tjoin_blocks(ctx, (uint64_t)a.rows));
   switch (stage) {
-    case 0: hipLaunchKernelGGL(tjoin_qprep_kernel, gq, blk, 0, s, a); break;
-    case 1: hipLaunchKernelGGL(tjoin_qrank_kernel, gq, blk, 0, s, a); break;
-    case 2: hipLaunchKernelGGL(tjoin_qscatter_kernel, gq, blk, 0, s, a); break;
-    case 3: hipLaunchKernelGGL(tjoin_runs_kernel, gq, blk, 0, s, a); break;
-    case 4: hipLaunchKernelGGL(tjoin_runend_kernel, gq, blk, 0, s, a); break;
-    case 5: hipLaunchKernelGGL(tjoin_ocell_kernel, go, blk, 0, s, a); break;
-    case 6: {
+    case kTjoinQueryKeys: hipLaunchKernelGGL(tjoin_qprep_kernel, gq, blk, 0, s, a); break;
+    case kTjoinQueryRank: hipLaunchKernelGGL(tjoin_qrank_kernel, gq, blk, 0, s, a); break;
+    case kTjoinQueryScatter: hipLaunchKernelGGL(tjoin_qscatter_kernel, gq, blk, 0, s, a); break;
+    case kTjoinRunStarts: hipLaunchKernelGGL(tjoin_runs_kernel, gq, blk, 0, s, a); break;
+    case kTjoinRunEnds: hipLaunchKernelGGL(tjoin_runend_kernel, gq, blk, 0, s, a); break;
+    case kTjoinCellKeys: hipLaunchKernelGGL(tjoin_ocell_kernel, go, blk, 0, s, a); break;
+    case kTjoinProbe: {
       // every lane walks its own bucket rows: as many blocks as there are points, so that the points of
       // one crowded cell (neighbours in the probe's order) spread over the CUs
       const uint64_t b = ((uint64_t)a.no + kBlock - 1) / kBlock;
       hipLaunchKernelGGL(tjoin_probe_kernel, dim3((unsigned)(b < 1 ? 1 : (b > (1u << 20) ? (1u << 20) : b))), blk, 0, s, a);
       break;
     }
-    case 7: hipLaunchKernelGGL(tjoin_occupied_kernel, gs, blk, 0, s, a); break;
-    case 8: hipLaunchKernelGGL(tjoin_compact_kernel, gs, blk, 0, s, a); break;
-    case 9: hipLaunchKernelGGL(tjoin_rows_kernel, gr, blk, 0, s, a); break;
-    case 10: hipLaunchKernelGGL(tjoin_slots_kernel, gr, blk, 0, s, a); break;
-    case 11: hipLaunchKernelGGL(tjoin_tlist_kernel, dim3(tjoin_blocks(ctx, (uint64_t)a.nt)), blk, 0, s, a); break;
-    case 12: hipLaunchKernelGGL(tjoin_totals_kernel, dim3(1), dim3(64), 0, s, a); break;
-    default:
+    case kTjoinOccupied: hipLaunchKernelGGL(tjoin_occupied_kernel, gs, blk, 0, s, a); break;
+    case kTjoinCompact: hipLaunchKernelGGL(tjoin_compact_kernel, gs, blk, 0, s, a); break;
+    case kTjoinRows: hipLaunchKernelGGL(tjoin_rows_kernel, gr, blk, 0, s, a); break;
+    case kTjoinRowSlots: hipLaunchKernelGGL(tjoin_slots_kernel, gr, blk, 0, s, a); break;
+    case kTjoinSideList: hipLaunchKernelGGL(tjoin_tlist_kernel, dim3(tjoin_blocks(ctx, (uint64_t)a.nt)), blk, 0, s, a); break;
+    case kTjoinTotals: hipLaunchKernelGGL(tjoin_totals_kernel, dim3(1), dim3(64), 0, s, a); break;
+    default:  // kTjoinGather
       hipLaunchKernelGGL(tjoin_gather_kernel, dim3(tjoin_blocks(ctx, (uint64_t)std::max(a.npts, a.m))), blk, 0, s, a);
       break;
   }

@@ -289,25 +289,27 @@ hipError_t launch_tknn(gf_ctx* ctx, int stage, const TknnArgs& a) {
   const dim3 gn(tknn_blocks(ctx, (uint64_t)a.n)), gm(tknn_blocks(ctx, (uint64_t)a.m)),
       gp(tknn_blocks(ctx, (uint64_t)a.npairs)), gt(tknn_blocks(ctx, (uint64_t)a.ntraj));
   switch (stage) {
-    case 0:
+    case kTknnScanWindow:
       hipLaunchKernelGGL(tknn_scan_kernel, dim3(tknn_blocks(ctx, ((uint64_t)a.n + kTknnScanU - 1) / kTknnScanU)), blk, 0, s, a);
       break;
-    case 1: hipLaunchKernelGGL(tknn_compose_kernel, gm, blk, 0, s, a); break;
-    case 2:
+    case kTknnCompose: hipLaunchKernelGGL(tknn_compose_kernel, gm, blk, 0, s, a); break;
+    case kTknnPairMin:
       hipLaunchKernelGGL(tknn_pair_init_kernel, gp, blk, 0, s, a);
       hipLaunchKernelGGL(tknn_pair_min_kernel, gm, blk, 0, s, a);
       hipLaunchKernelGGL(tknn_pair_nan_kernel, gm, blk, 0, s, a);
       break;
-    case 3: hipLaunchKernelGGL(tknn_rank_small_kernel, gp, blk, 0, s, a); break;
-    case 4: hipLaunchKernelGGL(tknn_rank_big_kernel, gp, blk, 0, s, a); break;
-    case 5:
+    case kTknnRankSmall: hipLaunchKernelGGL(tknn_rank_small_kernel, gp, blk, 0, s, a); break;
+    case kTknnRankBig: hipLaunchKernelGGL(tknn_rank_big_kernel, gp, blk, 0, s, a); break;
+    case kTknnCombine:
       hipLaunchKernelGGL(tknn_traj_init_kernel, gt, blk, 0, s, a);
       hipLaunchKernelGGL(tknn_combine_kernel, gp, blk, 0, s, a);
       hipLaunchKernelGGL(tknn_survive_kernel, gt, blk, 0, s, a);
       break;
-    case 6: hipLaunchKernelGGL(tknn_slist_kernel, gt, blk, 0, s, a); break;
-    case 7: hipLaunchKernelGGL(tknn_rows_kernel, dim3(tknn_blocks(ctx, (uint64_t)a.rows)), blk, 0, s, a); break;
-    default: hipLaunchKernelGGL(tknn_gather_kernel, dim3(tknn_blocks(ctx, (uint64_t)a.npts)), blk, 0, s, a); break;
+    case kTknnSurvivors: hipLaunchKernelGGL(tknn_slist_kernel, gt, blk, 0, s, a); break;
+    case kTknnRows: hipLaunchKernelGGL(tknn_rows_kernel, dim3(tknn_blocks(ctx, (uint64_t)a.rows)), blk, 0, s, a); break;
+    default:  // kTknnGather
+      hipLaunchKernelGGL(tknn_gather_kernel, dim3(tknn_blocks(ctx, (uint64_t)a.npts)), blk, 0, s, a);
+      break;
   }
   return hipGetLastError();
 }

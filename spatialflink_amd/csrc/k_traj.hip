@@ -133,16 +133,16 @@ hipError_t launch_traj_group(gf_ctx* ctx, int stage, const TrajGroupArgs& a) {
   KTimer timer(ctx, GF_K_TRAJ_GROUP);
   const unsigned g = traj_blocks(ctx, (uint64_t)a.n);
   switch (stage) {
-    case 0:
+    case kTrajGroupInsert:
       hipLaunchKernelGGL(traj_clear_kernel, dim3(traj_blocks(ctx, a.t.mask + 2)), dim3(kBlock), 0, s, a.t);
       hipLaunchKernelGGL(traj_insert_kernel, dim3(g), dim3(kBlock), 0, s, a.t, a.objID, a.n);
       hipLaunchKernelGGL(traj_flag_kernel, dim3(g), dim3(kBlock), 0, s, a.t, a.objID, a.n, a.flag);
       break;
-    case 1:
+    case kTrajGroupAssign:
       hipLaunchKernelGGL(traj_assign_kernel, dim3(g), dim3(kBlock), 0, s, a.t, a.objID, a.n, a.flag, a.rank, a.keys);
       hipLaunchKernelGGL(traj_ids_kernel, dim3(g), dim3(kBlock), 0, s, a.t, a.objID, a.n, a.did);
       break;
-    default:
+    default:  // kTrajGroupBounds
       hipLaunchKernelGGL(traj_bounds_kernel, dim3(g), dim3(kBlock), 0, s, a.sorted, a.n, a.ntraj, a.seg_off);
       break;
   }
@@ -336,7 +336,7 @@ hipError_t launch_tstats_filter(gf_ctx* ctx, const TStatsArgs& a, const int64_t*
                                 int stage) {
   KTimer timer(ctx, GF_K_TSTATS);
   const unsigned g = traj_blocks(ctx, (uint64_t)a.ntraj);
-  if (stage == 0)
+  if (stage == kTStatsFilterMark)
     hipLaunchKernelGGL(tstats_filter_kernel, dim3(g), dim3(kBlock), 0, ctx->stream, keys, a.ntraj, set, nset, sel);
   else
     hipLaunchKernelGGL(tstats_compact_kernel, dim3(g), dim3(kBlock), 0, ctx->stream, a, sel, rank, keys, ok, oS, oT, oV);
@@ -393,10 +393,10 @@ __global__ __launch_bounds__(kBlock) void traj_gather_kernel(TrajSelectArgs a) {
 hipError_t launch_traj_select(gf_ctx* ctx, int stage, const TrajSelectArgs& a) {
   KTimer timer(ctx, GF_K_TRAJ_SELECT);
   hipStream_t s = ctx->stream;
-  if (stage == 0) {
+  if (stage == kTrajSelectHit) {
     hipLaunchKernelGGL(traj_hit_kernel, dim3(traj_blocks(ctx, (uint64_t)a.n)), dim3(kBlock), 0, s, a.bitmap, a.did, a.n,
                        a.hit);
-  } else if (stage == 2) {
+  } else if (stage == kTrajSelectLens) {
     hipLaunchKernelGGL(traj_lens_kernel, dim3(traj_blocks(ctx, (uint64_t)a.ntraj)), dim3(kBlock), 0, s, a.hit, a.seg_off,
                        a.ntraj, a.len);
   } else {

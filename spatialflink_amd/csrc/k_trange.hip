@@ -229,11 +229,11 @@ hipError_t launch_trange(gf_ctx* ctx, int stage, const TrangeArgs& a) {
   hipStream_t s = ctx->stream;
   const dim3 blk(kBlock);
   const bool traj = a.did != nullptr;
-  if (stage == 0) {
+  if (stage == kTrangeMark) {
     const dim3 g(trange_blocks(ctx, (uint64_t)a.n));
     if (traj) hipLaunchKernelGGL(trange_mark_kernel<true>, g, blk, 0, s, a);
     else hipLaunchKernelGGL(trange_mark_kernel<false>, g, blk, 0, s, a);
-  } else if (stage == 1) {
+  } else if (stage == kTrangeWaves) {
     const dim3 g((unsigned)ctx->num_cus * 8);
     if (traj) hipLaunchKernelGGL(trange_wide_kernel<true>, g, blk, 0, s, a);
     else hipLaunchKernelGGL(trange_wide_kernel<false>, g, blk, 0, s, a);

@@ -2,7 +2,8 @@
 // 498-613): gf_tagg_group (a window grouped by (cell, objID)), gf_tagg_run (per-group and per-cell
 // statistics), the reads and the pure-host row rules (gf_tagg_rows).  The kernels are in k_tagg.hip;
 // the three groupings and the sort of the groups by cell are gf_group.hpp's (traj.cpp).  The object
-// owns its device workspace (grow-only) and is reused across windows.
+// is made of gf_group.hpp's typed device arrays (grow-only, freed by its destructor) and is reused
+// across windows.
 #define GF_TU_NAME tagg_cpp
 #include "gf_buildtag.hpp"  // first: records this unit's command-line defines
 
@@ -24,20 +25,12 @@ struct gf_tagg {
   bool ran = false;
   KeyGroups cells, objs, pairs;  // dense ids of pack(cx, cy), of objID, and the grouping of their pair
   KeyGroups bycell;              // the groups sorted by cell id (sort only)
-  DevBuf ckey, comp;
-  DevBuf g_cell, g_m, g_key, g_L, g_e, g_f, g_s, list, counters;
-  DevBuf c_cx, c_cy, c_count, c_multi, c_sum, c_minLen, c_minKey, c_maxLen, c_maxKey, all_key, all_len;
-  DevBuf* all[23] = {&ckey, &comp, &g_cell, &g_m, &g_key, &g_L, &g_e, &g_f, &g_s, &list, &counters, &c_cx,
-                     &c_cy, &c_count, &c_multi, &c_sum, &c_minLen, &c_minKey, &c_maxLen, &c_maxKey, &all_key, &all_len,
-                     nullptr};
+  DevArr<int64_t> ckey, comp;
+  DevArr<uint32_t> g_cell, g_m, g_f, g_s, list, counters;
+  DevArr<int64_t> g_key, g_L, g_e;
+  DevArr<int32_t> c_cx, c_cy;
+  DevArr<int64_t> c_count, c_multi, c_sum, c_minLen, c_minKey, c_maxLen, c_maxKey, all_key, all_len;
 };
-
-template <class T>
-static int read_back(gf_ctx* ctx, T* host, const void* dev, size_t count) {
-  if (!host || count == 0) return GF_OK;
-  GF_HIP_CHECK(ctx, hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-  return GF_OK;
-}
 
 extern "C" int gf_tagg_group(gf_ctx* ctx, const gf_grid* grid, const gf_points* pts, gf_tagg** out) {
   if (!ctx || !out || !pts || !grid) return set_err(ctx, GF_ERR_ARG, "gf_tagg_group: null argument");
@@ -63,23 +56,22 @@ extern "C" int gf_tagg_group(gf_ctx* ctx, const gf_grid* grid, const gf_points* 
     *out = G;
     return GF_OK;
   }
-  if ((st = G->ckey.reserve(ctx, sizeof(int64_t) * (size_t)n)) || (st = G->comp.reserve(ctx, sizeof(int64_t) * (size_t)n)))
-    return fail(st);
+  if ((st = G->ckey.reserve(ctx, (size_t)n)) || (st = G->comp.reserve(ctx, (size_t)n))) return fail(st);
   TaggArgs a{};
   a.x = pts->x; a.y = pts->y; a.n = n;
   a.minX = grid->minX; a.minY = grid->minY; a.cl = grid->cellLength;
-  a.ckey = G->ckey.as<int64_t>();
-  a.comp = G->comp.as<int64_t>();
-  hipError_t e = launch_tagg(ctx, 0, a);
+  a.ckey = G->ckey.p;
+  a.comp = G->comp.p;
+  hipError_t e = launch_tagg(ctx, kTaggCellKeys, a);
   if (e != hipSuccess) return fail(hip_err(ctx, e, "tagg cell keys"));
   if ((st = group_dense_ids(ctx, G->cells, a.ckey, n, "gf_tagg_group")) ||
       (st = group_dense_ids(ctx, G->objs, pts->objID, n, "gf_tagg_group")))
     return fail(st);
-  a.cid = G->cells.did.as<uint32_t>();
-  a.oid = G->objs.did.as<uint32_t>();
-  if ((e = launch_tagg(ctx, 1, a)) != hipSuccess) return fail(hip_err(ctx, e, "tagg pair keys"));
+  a.cid = G->cells.did.p;
+  a.oid = G->objs.did.p;
+  if ((e = launch_tagg(ctx, kTaggPairKeys, a)) != hipSuccess) return fail(hip_err(ctx, e, "tagg pair keys"));
   if ((st = group_dense_ids(ctx, G->pairs, a.comp, n, "gf_tagg_group")) ||
-      (st = group_sort_ids(ctx, G->pairs, G->pairs.did.as<uint32_t>(), n, (uint32_t)G->pairs.ngroups)))
+      (st = group_sort_ids(ctx, G->pairs, G->pairs.did.p, n, (uint32_t)G->pairs.ngroups)))
     return fail(st);
   if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(hip_err(ctx, e, "gf_tagg_group"));
   G->ncells = G->cells.ngroups;
@@ -101,45 +93,41 @@ extern "C" int gf_tagg_run(gf_tagg* G, const gf_points* pts) {
   int st = bind(ctx);
   if (st) return st;
   const size_t ng = (size_t)G->ngroups, nc = (size_t)G->ncells;
-  if ((st = G->g_cell.reserve(ctx, ng * 4)) || (st = G->g_m.reserve(ctx, ng * 4)) || (st = G->g_key.reserve(ctx, ng * 8)) ||
-      (st = G->g_L.reserve(ctx, ng * 8)) || (st = G->g_e.reserve(ctx, ng * 8)) || (st = G->g_f.reserve(ctx, ng * 4)) ||
-      (st = G->g_s.reserve(ctx, ng * 4)) || (st = G->list.reserve(ctx, nc * 4)) || (st = G->counters.reserve(ctx, 16)) ||
-      (st = G->c_cx.reserve(ctx, nc * 4)) || (st = G->c_cy.reserve(ctx, nc * 4)) || (st = G->c_count.reserve(ctx, nc * 8)) ||
-      (st = G->c_multi.reserve(ctx, nc * 8)) || (st = G->c_sum.reserve(ctx, nc * 8)) ||
-      (st = G->c_minLen.reserve(ctx, nc * 8)) || (st = G->c_minKey.reserve(ctx, nc * 8)) ||
-      (st = G->c_maxLen.reserve(ctx, nc * 8)) || (st = G->c_maxKey.reserve(ctx, nc * 8)) ||
-      (st = G->all_key.reserve(ctx, ng * 8)) || (st = G->all_len.reserve(ctx, ng * 8)))
+  if ((st = G->g_cell.reserve(ctx, ng)) || (st = G->g_m.reserve(ctx, ng)) || (st = G->g_key.reserve(ctx, ng)) ||
+      (st = G->g_L.reserve(ctx, ng)) || (st = G->g_e.reserve(ctx, ng)) || (st = G->g_f.reserve(ctx, ng)) ||
+      (st = G->g_s.reserve(ctx, ng)) || (st = G->list.reserve(ctx, nc)) || (st = G->counters.reserve(ctx, kCounterWords)) ||
+      (st = G->c_cx.reserve(ctx, nc)) || (st = G->c_cy.reserve(ctx, nc)) || (st = G->c_count.reserve(ctx, nc)) ||
+      (st = G->c_multi.reserve(ctx, nc)) || (st = G->c_sum.reserve(ctx, nc)) || (st = G->c_minLen.reserve(ctx, nc)) ||
+      (st = G->c_minKey.reserve(ctx, nc)) || (st = G->c_maxLen.reserve(ctx, nc)) || (st = G->c_maxKey.reserve(ctx, nc)) ||
+      (st = G->all_key.reserve(ctx, ng)) || (st = G->all_len.reserve(ctx, ng)))
     return st;
   TaggArgs a{};
   a.n = G->n;
   a.ts = pts->ts;
-  a.perm = G->pairs.perm.as<uint32_t>();
-  a.seg_off = G->pairs.seg_off.as<uint32_t>();
-  a.sorted = G->pairs.kbuf[G->pairs.sorted_in].as<uint32_t>();
-  a.gkeys = G->pairs.keys.as<int64_t>();
-  a.okeys = G->objs.keys.as<int64_t>();
+  a.perm = G->pairs.perm.p;
+  a.seg_off = G->pairs.seg_off.p;
+  a.sorted = G->pairs.kbuf[G->pairs.sorted_in].p;
+  a.gkeys = G->pairs.keys.p;
+  a.okeys = G->objs.keys.p;
   a.ngroups = G->ngroups;
   a.long_len = (uint32_t)G->long_len;
-  a.g_cell = G->g_cell.as<uint32_t>(); a.g_m = G->g_m.as<uint32_t>(); a.g_key = G->g_key.as<int64_t>();
-  a.g_L = G->g_L.as<int64_t>(); a.g_e = G->g_e.as<int64_t>(); a.g_f = G->g_f.as<uint32_t>(); a.g_s = G->g_s.as<uint32_t>();
-  a.list = G->list.as<uint32_t>();
-  a.list_count = G->counters.as<uint32_t>();
-  GF_HIP_CHECK(ctx, hipMemsetAsync(G->counters.p, 0, 16, ctx->stream));
-  GF_HIP_CHECK(ctx, launch_tagg(ctx, 2, a));
+  a.g_cell = G->g_cell.p; a.g_m = G->g_m.p; a.g_key = G->g_key.p; a.g_L = G->g_L.p; a.g_e = G->g_e.p;
+  a.g_f = G->g_f.p; a.g_s = G->g_s.p; a.list = G->list.p;
+  a.list_count = G->counters.p;
+  GF_HIP_CHECK(ctx, hipMemsetAsync(G->counters.p, 0, kCounterWords * sizeof(uint32_t), ctx->stream));
+  GF_HIP_CHECK(ctx, launch_tagg(ctx, kTaggGroupStats, a));
   // the groups sorted stably by cell id (every cell has a group): a cell's groups stay in first-occurrence order
   if ((st = group_sort_ids(ctx, G->bycell, a.g_cell, G->ngroups, (uint32_t)G->ncells))) return st;
-  a.gperm = G->bycell.perm.as<uint32_t>();
-  a.cell_off = G->bycell.seg_off.as<uint32_t>();
-  a.ckeys = G->cells.keys.as<int64_t>();
+  a.gperm = G->bycell.perm.p;
+  a.cell_off = G->bycell.seg_off.p;
+  a.ckeys = G->cells.keys.p;
   a.ncells = G->ncells;
   a.big_cell = (uint32_t)G->big_cell;
-  a.list_count = G->counters.as<uint32_t>() + 1;
-  a.c_cx = G->c_cx.as<int32_t>(); a.c_cy = G->c_cy.as<int32_t>();
-  a.c_count = G->c_count.as<int64_t>(); a.c_multi = G->c_multi.as<int64_t>(); a.c_sum = G->c_sum.as<int64_t>();
-  a.c_minLen = G->c_minLen.as<int64_t>(); a.c_minKey = G->c_minKey.as<int64_t>();
-  a.c_maxLen = G->c_maxLen.as<int64_t>(); a.c_maxKey = G->c_maxKey.as<int64_t>();
-  a.all_key = G->all_key.as<int64_t>(); a.all_len = G->all_len.as<int64_t>();
-  GF_HIP_CHECK(ctx, launch_tagg(ctx, 3, a));
+  a.list_count = G->counters.p + 1;
+  a.c_cx = G->c_cx.p; a.c_cy = G->c_cy.p; a.c_count = G->c_count.p; a.c_multi = G->c_multi.p; a.c_sum = G->c_sum.p;
+  a.c_minLen = G->c_minLen.p; a.c_minKey = G->c_minKey.p; a.c_maxLen = G->c_maxLen.p; a.c_maxKey = G->c_maxKey.p;
+  a.all_key = G->all_key.p; a.all_len = G->all_len.p;
+  GF_HIP_CHECK(ctx, launch_tagg(ctx, kTaggCells, a));
   GF_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   G->ran = true;
   return GF_OK;
@@ -151,11 +139,6 @@ extern "C" void gf_tagg_destroy(gf_tagg* G) {
     hipSetDevice(G->ctx->device);
     hipStreamSynchronize(G->ctx->stream);
   }
-  G->cells.release_groups();
-  G->objs.release_groups();
-  G->pairs.release_groups();
-  G->bycell.release_groups();
-  for (DevBuf** b = G->all; *b; ++b) (*b)->release();
   delete G;
 }
 
@@ -210,13 +193,12 @@ extern "C" int gf_tagg_read_all(gf_tagg* G, int64_t* off, int64_t* keys, int64_t
   int st = bind(ctx);
   if (st) return st;
   const size_t wc = (size_t)std::min(G->ncells, cap_cells), wg = (size_t)std::min(G->ngroups, cap_groups);
-  std::vector<uint32_t> ho;
-  if (off) ho.resize(wc + 1);
-  if ((st = read_back(ctx, off ? ho.data() : nullptr, G->bycell.seg_off.p, ho.size())) ||
-      (st = read_back(ctx, keys, G->all_key.p, wg)) || (st = read_back(ctx, len, G->all_len.p, wg)))
+  OffsetRead ho;
+  if ((st = read_offsets(ctx, ho, off, G->bycell.seg_off.p, wc + 1)) || (st = read_back(ctx, keys, G->all_key.p, wg)) ||
+      (st = read_back(ctx, len, G->all_len.p, wg)))
     return st;
   GF_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  for (size_t i = 0; i < ho.size(); ++i) off[i] = (int64_t)ho[i];
+  ho.widen();
   return GF_OK;
 }
 

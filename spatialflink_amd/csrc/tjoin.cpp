@@ -2,8 +2,9 @@
 // commonSingle, TJoinQuery.java): gf_tjoin_run over two windows already grouped by objID
 // (gf_traj_group), the reads and the testing hook.  The kernels are in k_tjoin.hip; the multi-word sorts
 // are gf_group.hpp's (traj.cpp) on k_points.hip's radix passes, the query side's clamped bucket key is
-// k_join.hip's launch_join_qkeys.  The object owns its device workspace (grow-only), the row table
-// included, and is reused across windows; the table's growth loop lives here.
+// k_join.hip's launch_join_qkeys.  The object is made of gf_group.hpp's typed device arrays (grow-only,
+// freed by its destructor), the row table included, and is reused across windows; the table's growth
+// loop lives here.
 #define GF_TU_NAME tjoin_cpp
 #include "gf_buildtag.hpp"  // first: records this unit's command-line defines
 
@@ -23,34 +24,27 @@ struct gf_tjoin {
   int64_t slots = 0;       // the table of the last window (0: none yet)
   int64_t want_slots = 0;  // testing: the next run's first table size (0: slots, or the default)
   KeyGroups srt;           // the sorts' radix workspace and the scans' scratch
-  DevBuf wkey, sp[2];
-  DevBuf bkey, qcx, qcy, its, comp, qrank, qord, sxy, smeta, sqr, flag, fscan, rstart, boff, ocell, tkey, tqr, tpf, tcount,
-      occ, cpos, rkey, rqr, rpf, o_okey, o_qkey, o_pfirst, o_qlatest, o_emit, o_oslot, o_qslot, o_to, o_tq, counters;
-  DevBuf mark[2], mrank[2], tlist[2], tlen[2], toff[2], c_keys[2], c_x[2], c_y[2], c_ts[2], c_idx[2];
-  std::vector<DevBuf*> all() {
-    std::vector<DevBuf*> v = {&wkey, &sp[0], &sp[1], &bkey, &qcx, &qcy, &its, &comp, &qrank, &qord, &sxy, &smeta, &sqr,
-                              &flag, &fscan, &rstart, &boff, &ocell, &tkey, &tqr, &tpf, &tcount, &occ, &cpos, &rkey,
-                              &rqr, &rpf, &o_okey, &o_qkey, &o_pfirst, &o_qlatest, &o_emit, &o_oslot, &o_qslot, &o_to,
-                              &o_tq, &counters};
-    for (int s = 0; s < 2; ++s)
-      for (DevBuf* b : {&mark[s], &mrank[s], &tlist[s], &tlen[s], &toff[s], &c_keys[s], &c_x[s], &c_y[s], &c_ts[s], &c_idx[s]})
-        v.push_back(b);
-    return v;
-  }
+  DevArr<uint32_t> wkey, sp[2];
+  // the query side in bucket order, the ordinary side's cell keys
+  DevArr<uint32_t> bkey, qrank, qord, sqr, flag, fscan, rstart, boff;
+  DevArr<int32_t> qcx, qcy;
+  DevArr<unsigned long long> its, comp, ocell;
+  DevArr<double2> sxy;
+  DevArr<int4> smeta;
+  // the row table, the rows
+  DevArr<unsigned long long> tkey, rkey;
+  DevArr<uint32_t> tqr, tpf, tcount, occ, cpos, rqr, rpf, o_pfirst, o_qlatest, o_to, o_tq, counters;
+  DevArr<int64_t> o_okey, o_qkey;
+  DevArr<uint8_t> o_emit;
+  DevArr<int32_t> o_oslot, o_qslot;
+  // per side: the emitted trajectories' CSR
+  DevArr<uint32_t> mark[2], mrank[2], tlist[2], tlen[2], toff[2], c_idx[2];
+  DevArr<int64_t> c_keys[2], c_ts[2];
+  DevArr<double> c_x[2], c_y[2];
 };
 
-template <class T>
-static int read_back(gf_ctx* ctx, T* host, const void* dev, size_t count) {
-  if (!host || count == 0) return GF_OK;
-  GF_HIP_CHECK(ctx, hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-  return GF_OK;
-}
-
-static int key_bits(uint64_t nids) {
-  int bits = 1;
-  while (((uint64_t)1 << bits) < nids) ++bits;
-  return bits;
-}
+constexpr size_t kTjoinCounterWords = 8;  // TjoinArgs::counters
+constexpr size_t kTjoinCountWords = (size_t)kTjoinMaxShards * kTjoinShardStride + 1;  // TjoinTable::count, then the overflow word
 
 static int64_t pow2_at_least(double v) {
   int64_t p = kTjoinMinSlots;
@@ -65,37 +59,32 @@ static int tjoin_query_side(gf_tjoin* T, gf_traj_groups* gq, const gf_points* qp
   const int64_t nq = gq->n, ntq = gq->ntraj, W = (int64_t)grid->n + 2;
   const size_t z = (size_t)nq;
   a.nb = W * W;
-  if ((st = T->bkey.reserve(ctx, z * 4)) || (st = T->qcx.reserve(ctx, z * 4)) || (st = T->qcy.reserve(ctx, z * 4)) ||
-      (st = T->its.reserve(ctx, z * 8)) || (st = T->comp.reserve(ctx, z * 8)) || (st = T->qrank.reserve(ctx, z * 4)) ||
-      (st = T->qord.reserve(ctx, z * 4)) || (st = T->sxy.reserve(ctx, z * 16)) || (st = T->smeta.reserve(ctx, z * 16)) ||
-      (st = T->sqr.reserve(ctx, z * 4)) || (st = T->flag.reserve(ctx, (z + 1) * 4)) ||
-      (st = T->fscan.reserve(ctx, (z + 1) * 4)) || (st = T->rstart.reserve(ctx, (z + 1) * 4)) ||
-      (st = T->boff.reserve(ctx, ((size_t)a.nb + 1) * 4)))
+  if ((st = T->bkey.reserve(ctx, z)) || (st = T->qcx.reserve(ctx, z)) || (st = T->qcy.reserve(ctx, z)) ||
+      (st = T->its.reserve(ctx, z)) || (st = T->comp.reserve(ctx, z)) || (st = T->qrank.reserve(ctx, z)) ||
+      (st = T->qord.reserve(ctx, z)) || (st = T->sxy.reserve(ctx, z)) || (st = T->smeta.reserve(ctx, z)) ||
+      (st = T->sqr.reserve(ctx, z)) || (st = T->flag.reserve(ctx, z + 1)) || (st = T->fscan.reserve(ctx, z + 1)) ||
+      (st = T->rstart.reserve(ctx, z + 1)) || (st = T->boff.reserve(ctx, (size_t)a.nb + 1)))
     return st;
   a.qx = qpts->x; a.qy = qpts->y; a.qts = qpts->ts;
-  a.qdid = gq->did.as<uint32_t>(); a.qseg = gq->seg_off.as<uint32_t>(); a.qperm = gq->perm.as<uint32_t>();
-  a.qkeys = gq->keys.as<int64_t>();
+  a.qdid = gq->did.p; a.qseg = gq->seg_off.p; a.qperm = gq->perm.p; a.qkeys = gq->keys.p;
   a.nq = nq; a.ntq = ntq;
-  a.bkey = T->bkey.as<uint32_t>(); a.qcx = T->qcx.as<int32_t>(); a.qcy = T->qcy.as<int32_t>();
-  a.its = T->its.as<unsigned long long>(); a.comp = T->comp.as<unsigned long long>();
-  a.qrank = T->qrank.as<uint32_t>(); a.qord = T->qord.as<uint32_t>();
-  a.sxy = T->sxy.as<double2>(); a.smeta = T->smeta.as<int4>(); a.sqr = T->sqr.as<uint32_t>();
-  a.flag = T->flag.as<uint32_t>(); a.fscan = T->fscan.as<uint32_t>(); a.rstart = T->rstart.as<uint32_t>();
-  a.boff = T->boff.as<uint32_t>();
+  a.bkey = T->bkey.p; a.qcx = T->qcx.p; a.qcy = T->qcy.p; a.its = T->its.p; a.comp = T->comp.p;
+  a.qrank = T->qrank.p; a.qord = T->qord.p; a.sxy = T->sxy.p; a.smeta = T->smeta.p; a.sqr = T->sqr.p;
+  a.flag = T->flag.p; a.fscan = T->fscan.p; a.rstart = T->rstart.p; a.boff = T->boff.p;
   GF_HIP_CHECK(ctx, launch_join_qkeys(ctx->stream, a.qx, a.qy, nq, grid->minX, grid->minY, grid->cellLength, grid->n,
-                                      T->bkey.as<uint32_t>(), T->qcx.as<int32_t>(), T->qcy.as<int32_t>()));
-  GF_HIP_CHECK(ctx, launch_tjoin(ctx, 0, a));
+                                      T->bkey.p, T->qcx.p, T->qcy.p));
+  GF_HIP_CHECK(ctx, launch_tjoin(ctx, kTjoinQueryKeys, a));
   // (trajectory, ts descending, index): the inverted ts words, then the trajectory, least significant first
   const SortWord w3[3] = {{a.its, nullptr, 0, 32}, {a.its, nullptr, 32, 32}, {a.comp, nullptr, 0, key_bits((uint64_t)ntq)}};
   if ((st = group_sort_words(ctx, T->srt, T->wkey, T->sp, w3, 3, nq, nullptr, &a.ord))) return st;
-  GF_HIP_CHECK(ctx, launch_tjoin(ctx, 1, a));
+  GF_HIP_CHECK(ctx, launch_tjoin(ctx, kTjoinQueryRank, a));
   // stably by bucket over that order: every bucket sorted by (trajectory, qrank)
   const SortWord wb[1] = {{a.comp, nullptr, 32, key_bits((uint64_t)a.nb)}};
   if ((st = group_sort_words(ctx, T->srt, T->wkey, T->sp, wb, 1, nq, a.qord, &a.sidx))) return st;
-  GF_HIP_CHECK(ctx, launch_tjoin(ctx, 2, a));
-  if ((st = group_scan_u32(ctx, T->srt, a.flag, nq, T->fscan.as<uint32_t>()))) return st;
-  GF_HIP_CHECK(ctx, launch_tjoin(ctx, 3, a));
-  GF_HIP_CHECK(ctx, launch_tjoin(ctx, 4, a));
+  GF_HIP_CHECK(ctx, launch_tjoin(ctx, kTjoinQueryScatter, a));
+  if ((st = group_scan_u32(ctx, T->srt, a.flag, nq, T->fscan.p))) return st;
+  GF_HIP_CHECK(ctx, launch_tjoin(ctx, kTjoinRunStarts, a));
+  GF_HIP_CHECK(ctx, launch_tjoin(ctx, kTjoinRunEnds, a));
   return GF_OK;
 }
 
@@ -106,24 +95,24 @@ static int tjoin_table(gf_tjoin* T, int64_t slots, TjoinArgs& a) {
   const size_t z = (size_t)slots;
   uint32_t shards = 1;
   while (shards < kTjoinMaxShards && (int64_t)shards * 2048 <= slots) shards <<= 1;  // >= 512 rows a shard
-  const size_t cbytes = (size_t)shards * kTjoinShardStride * 4 + 4;  // the counters, then the overflow word
-  if ((st = T->tkey.reserve(ctx, z * 8)) || (st = T->tqr.reserve(ctx, z * 4)) || (st = T->tpf.reserve(ctx, z * 4)) ||
-      (st = T->tcount.reserve(ctx, (size_t)kTjoinMaxShards * kTjoinShardStride * 4 + 4)))
+  const size_t cwords = (size_t)shards * kTjoinShardStride + 1;  // the counters, then the overflow word
+  if ((st = T->tkey.reserve(ctx, z)) || (st = T->tqr.reserve(ctx, z)) || (st = T->tpf.reserve(ctx, z)) ||
+      (st = T->tcount.reserve(ctx, kTjoinCountWords)))
     return st;
-  a.t.key = T->tkey.as<unsigned long long>();
-  a.t.qrank = T->tqr.as<uint32_t>();
-  a.t.pfirst = T->tpf.as<uint32_t>();
+  a.t.key = T->tkey.p;
+  a.t.qrank = T->tqr.p;
+  a.t.pfirst = T->tpf.p;
   a.t.mask = (uint64_t)slots - 1;
-  a.t.count = T->tcount.as<uint32_t>();
+  a.t.count = T->tcount.p;
   a.t.overflow = a.t.count + (size_t)shards * kTjoinShardStride;
   a.t.shard_shift = (uint32_t)(key_bits((uint64_t)slots) - key_bits((uint64_t)shards));  // (both powers of two; 1 shard: >= the key's bits)
   if (shards == 1) a.t.shard_shift = 63;
   a.t.shard_cap = (uint32_t)(slots / 2 / shards);
   a.slots = slots;
-  GF_HIP_CHECK(ctx, hipMemsetAsync(a.t.key, 0xFF, z * 8, ctx->stream));
-  GF_HIP_CHECK(ctx, hipMemsetAsync(a.t.qrank, 0xFF, z * 4, ctx->stream));
-  GF_HIP_CHECK(ctx, hipMemsetAsync(a.t.pfirst, 0xFF, z * 4, ctx->stream));
-  GF_HIP_CHECK(ctx, hipMemsetAsync(a.t.count, 0, cbytes, ctx->stream));
+  GF_HIP_CHECK(ctx, hipMemsetAsync(a.t.key, 0xFF, z * sizeof *a.t.key, ctx->stream));
+  GF_HIP_CHECK(ctx, hipMemsetAsync(a.t.qrank, 0xFF, z * sizeof *a.t.qrank, ctx->stream));
+  GF_HIP_CHECK(ctx, hipMemsetAsync(a.t.pfirst, 0xFF, z * sizeof *a.t.pfirst, ctx->stream));
+  GF_HIP_CHECK(ctx, hipMemsetAsync(a.t.count, 0, cwords * sizeof *a.t.count, ctx->stream));
   return GF_OK;
 }
 
@@ -132,12 +121,12 @@ static int tjoin_side_lists(gf_tjoin* T, int side, TjoinArgs& a) {
   gf_ctx* ctx = T->ctx;
   int st = GF_OK;
   const int64_t nt = side ? a.ntq : a.nto;
-  if ((st = group_scan_u32(ctx, T->srt, a.mark[side], nt, T->mrank[side].as<uint32_t>()))) return st;
-  GF_HIP_CHECK(ctx, hipMemsetAsync(T->tlen[side].p, 0, ((size_t)nt + 1) * 4, ctx->stream));
+  if ((st = group_scan_u32(ctx, T->srt, a.mark[side], nt, T->mrank[side].p))) return st;
+  GF_HIP_CHECK(ctx, hipMemsetAsync(T->tlen[side].p, 0, ((size_t)nt + 1) * sizeof(uint32_t), ctx->stream));
   a.side = side;
   a.nt = nt;
-  GF_HIP_CHECK(ctx, launch_tjoin(ctx, 11, a));
-  return group_scan_u32(ctx, T->srt, a.tlen[side], nt, T->toff[side].as<uint32_t>());
+  GF_HIP_CHECK(ctx, launch_tjoin(ctx, kTjoinSideList, a));
+  return group_scan_u32(ctx, T->srt, a.tlen[side], nt, T->toff[side].p);
 }
 
 static int tjoin_window(gf_tjoin* T, gf_traj_groups* go, const gf_points* opts, gf_traj_groups* gq, const gf_points* qpts,
@@ -149,14 +138,13 @@ static int tjoin_window(gf_tjoin* T, gf_traj_groups* go, const gf_points* opts, 
   if ((st = tjoin_query_side(T, gq, qpts, grid, a))) return st;
   // the ordinary side, sorted by cell for the probe
   a.ox = opts->x; a.oy = opts->y; a.ots = opts->ts;
-  a.odid = go->did.as<uint32_t>(); a.oseg = go->seg_off.as<uint32_t>(); a.operm = go->perm.as<uint32_t>();
-  a.okeys = go->keys.as<int64_t>();
+  a.odid = go->did.p; a.oseg = go->seg_off.p; a.operm = go->perm.p; a.okeys = go->keys.p;
   a.no = no; a.nto = nto;
   a.minX = grid->minX; a.minY = grid->minY; a.cl = grid->cellLength; a.r = r;
   a.qn = grid->n; a.c = c; a.single = single;
-  if ((st = T->ocell.reserve(ctx, (size_t)no * 8))) return st;
-  a.ocell = T->ocell.as<unsigned long long>();
-  GF_HIP_CHECK(ctx, launch_tjoin(ctx, 5, a));
+  if ((st = T->ocell.reserve(ctx, (size_t)no))) return st;
+  a.ocell = T->ocell.p;
+  GF_HIP_CHECK(ctx, launch_tjoin(ctx, kTjoinCellKeys, a));
   const SortWord wo[1] = {{a.ocell, nullptr, 0, key_bits((uint64_t)grid->n * (uint64_t)grid->n + 1)}};
   if ((st = group_sort_words(ctx, T->srt, T->wkey, T->sp, wo, 1, no, nullptr, &a.oord))) return st;
   // The probe, again with a table twice the size while it overflows.  No row table is larger than
@@ -168,10 +156,10 @@ static int tjoin_window(gf_tjoin* T, gf_traj_groups* go, const gf_points* opts, 
   for (;;) {
     size_t free_b = 0, total_b = 0;
     GF_HIP_CHECK(ctx, hipMemGetInfo(&free_b, &total_b));
-    const size_t held = T->tkey.bytes + T->tqr.bytes + T->tpf.bytes, need = (size_t)slots * 16;
+    const size_t held = T->tkey.bytes() + T->tqr.bytes() + T->tpf.bytes(), need = (size_t)slots * 16;
     if (need > held && need - held > free_b) return set_err(ctx, GF_ERR_NOMEM, "gf_tjoin_run: the row table does not fit the device memory");
     if ((st = tjoin_table(T, slots, a))) return st;
-    GF_HIP_CHECK(ctx, launch_tjoin(ctx, 6, a));
+    GF_HIP_CHECK(ctx, launch_tjoin(ctx, kTjoinProbe, a));
     ++T->passes;
     uint32_t ovf = 0;
     if ((st = read_scalar_sync(ctx, a.t.overflow, &ovf))) return st;
@@ -181,11 +169,11 @@ static int tjoin_window(gf_tjoin* T, gf_traj_groups* go, const gf_points* opts, 
   }
   T->slots = slots;
   // the rows: the occupied slots packed, then sorted by (t_o, t_q)
-  if ((st = T->occ.reserve(ctx, ((size_t)slots + 1) * 4)) || (st = T->cpos.reserve(ctx, ((size_t)slots + 1) * 4))) return st;
-  a.occ = T->occ.as<uint32_t>();
-  a.cpos = T->cpos.as<uint32_t>();
-  GF_HIP_CHECK(ctx, launch_tjoin(ctx, 7, a));
-  if ((st = group_scan_u32(ctx, T->srt, a.occ, slots, T->cpos.as<uint32_t>()))) return st;
+  if ((st = T->occ.reserve(ctx, (size_t)slots + 1)) || (st = T->cpos.reserve(ctx, (size_t)slots + 1))) return st;
+  a.occ = T->occ.p;
+  a.cpos = T->cpos.p;
+  GF_HIP_CHECK(ctx, launch_tjoin(ctx, kTjoinOccupied, a));
+  if ((st = group_scan_u32(ctx, T->srt, a.occ, slots, T->cpos.p))) return st;
   uint32_t rows32 = 0;
   if ((st = read_scalar_sync(ctx, a.cpos + slots, &rows32))) return st;
   const int64_t rows = rows32;
@@ -193,39 +181,36 @@ static int tjoin_window(gf_tjoin* T, gf_traj_groups* go, const gf_points* opts, 
   T->rows = rows;
   if (rows == 0) return GF_OK;
   const size_t nr = (size_t)rows;
-  if ((st = T->rkey.reserve(ctx, nr * 8)) || (st = T->rqr.reserve(ctx, nr * 4)) || (st = T->rpf.reserve(ctx, nr * 4)) ||
-      (st = T->o_okey.reserve(ctx, nr * 8)) || (st = T->o_qkey.reserve(ctx, nr * 8)) || (st = T->o_pfirst.reserve(ctx, nr * 4)) ||
-      (st = T->o_qlatest.reserve(ctx, nr * 4)) || (st = T->o_emit.reserve(ctx, nr)) || (st = T->o_oslot.reserve(ctx, nr * 4)) ||
-      (st = T->o_qslot.reserve(ctx, nr * 4)) || (st = T->o_to.reserve(ctx, nr * 4)) || (st = T->o_tq.reserve(ctx, nr * 4)) ||
-      (st = T->counters.reserve(ctx, 32)))
+  if ((st = T->rkey.reserve(ctx, nr)) || (st = T->rqr.reserve(ctx, nr)) || (st = T->rpf.reserve(ctx, nr)) ||
+      (st = T->o_okey.reserve(ctx, nr)) || (st = T->o_qkey.reserve(ctx, nr)) || (st = T->o_pfirst.reserve(ctx, nr)) ||
+      (st = T->o_qlatest.reserve(ctx, nr)) || (st = T->o_emit.reserve(ctx, nr)) || (st = T->o_oslot.reserve(ctx, nr)) ||
+      (st = T->o_qslot.reserve(ctx, nr)) || (st = T->o_to.reserve(ctx, nr)) || (st = T->o_tq.reserve(ctx, nr)) ||
+      (st = T->counters.reserve(ctx, kTjoinCounterWords)))
     return st;
   const int64_t nts[2] = {nto, ntq};
   for (int s = 0; s < 2; ++s) {
-    const size_t w = ((size_t)nts[s] + 1) * 4;
+    const size_t w = (size_t)nts[s] + 1;
     if ((st = T->mark[s].reserve(ctx, w)) || (st = T->mrank[s].reserve(ctx, w)) || (st = T->tlist[s].reserve(ctx, w)) ||
         (st = T->tlen[s].reserve(ctx, w)) || (st = T->toff[s].reserve(ctx, w)))
       return st;
-    GF_HIP_CHECK(ctx, hipMemsetAsync(T->mark[s].p, 0, w, ctx->stream));
-    a.mark[s] = T->mark[s].as<uint32_t>(); a.mrank[s] = T->mrank[s].as<uint32_t>();
-    a.tlist[s] = T->tlist[s].as<uint32_t>(); a.tlen[s] = T->tlen[s].as<uint32_t>(); a.toff[s] = T->toff[s].as<uint32_t>();
+    GF_HIP_CHECK(ctx, hipMemsetAsync(T->mark[s].p, 0, w * sizeof(uint32_t), ctx->stream));
+    a.mark[s] = T->mark[s].p; a.mrank[s] = T->mrank[s].p; a.tlist[s] = T->tlist[s].p; a.tlen[s] = T->tlen[s].p;
+    a.toff[s] = T->toff[s].p;
   }
   a.rows = rows;
-  a.rkey = T->rkey.as<unsigned long long>(); a.rqr = T->rqr.as<uint32_t>(); a.rpf = T->rpf.as<uint32_t>();
-  a.o_okey = T->o_okey.as<int64_t>(); a.o_qkey = T->o_qkey.as<int64_t>();
-  a.o_pfirst = T->o_pfirst.as<uint32_t>(); a.o_qlatest = T->o_qlatest.as<uint32_t>(); a.o_emit = T->o_emit.as<uint8_t>();
-  a.o_oslot = T->o_oslot.as<int32_t>(); a.o_qslot = T->o_qslot.as<int32_t>();
-  a.o_to = T->o_to.as<uint32_t>(); a.o_tq = T->o_tq.as<uint32_t>();
-  a.counters = T->counters.as<uint32_t>();
-  GF_HIP_CHECK(ctx, hipMemsetAsync(a.counters, 0, 32, ctx->stream));
-  GF_HIP_CHECK(ctx, launch_tjoin(ctx, 8, a));
+  a.rkey = T->rkey.p; a.rqr = T->rqr.p; a.rpf = T->rpf.p; a.o_okey = T->o_okey.p; a.o_qkey = T->o_qkey.p;
+  a.o_pfirst = T->o_pfirst.p; a.o_qlatest = T->o_qlatest.p; a.o_emit = T->o_emit.p; a.o_oslot = T->o_oslot.p;
+  a.o_qslot = T->o_qslot.p; a.o_to = T->o_to.p; a.o_tq = T->o_tq.p; a.counters = T->counters.p;
+  GF_HIP_CHECK(ctx, hipMemsetAsync(a.counters, 0, kTjoinCounterWords * sizeof(uint32_t), ctx->stream));
+  GF_HIP_CHECK(ctx, launch_tjoin(ctx, kTjoinCompact, a));
   const SortWord wr[2] = {{a.rkey, nullptr, 0, key_bits((uint64_t)ntq)}, {a.rkey, nullptr, 32, key_bits((uint64_t)nto)}};
   if ((st = group_sort_words(ctx, T->srt, T->wkey, T->sp, wr, 2, rows, nullptr, &a.rorder))) return st;
-  GF_HIP_CHECK(ctx, launch_tjoin(ctx, 9, a));
+  GF_HIP_CHECK(ctx, launch_tjoin(ctx, kTjoinRows, a));
   // the emitted rows' trajectories per side, their slots, their CSR
   if ((st = tjoin_side_lists(T, 0, a)) || (st = tjoin_side_lists(T, 1, a))) return st;
-  GF_HIP_CHECK(ctx, launch_tjoin(ctx, 10, a));
-  GF_HIP_CHECK(ctx, launch_tjoin(ctx, 12, a));
-  struct Totals { uint32_t v[8]; } tot{};
+  GF_HIP_CHECK(ctx, launch_tjoin(ctx, kTjoinRowSlots, a));
+  GF_HIP_CHECK(ctx, launch_tjoin(ctx, kTjoinTotals, a));
+  struct Totals { uint32_t v[kTjoinCounterWords]; } tot{};
   if ((st = read_scalar_sync(ctx, a.counters, &tot))) return st;
   T->emitted = tot.v[0];
   T->m[0] = tot.v[1]; T->npts[0] = tot.v[2];
@@ -235,14 +220,13 @@ static int tjoin_window(gf_tjoin* T, gf_traj_groups* go, const gf_points* opts, 
   for (int s = 0; s < 2; ++s) {
     if (T->m[s] == 0) continue;
     const size_t zm = (size_t)T->m[s], zp = (size_t)T->npts[s];
-    if ((st = T->c_keys[s].reserve(ctx, zm * 8)) || (st = T->c_x[s].reserve(ctx, zp * 8)) || (st = T->c_y[s].reserve(ctx, zp * 8)) ||
-        (st = T->c_ts[s].reserve(ctx, zp * 8)) || (st = T->c_idx[s].reserve(ctx, zp * 4)))
+    if ((st = T->c_keys[s].reserve(ctx, zm)) || (st = T->c_x[s].reserve(ctx, zp)) || (st = T->c_y[s].reserve(ctx, zp)) ||
+        (st = T->c_ts[s].reserve(ctx, zp)) || (st = T->c_idx[s].reserve(ctx, zp)))
       return st;
     a.side = s;
     a.m = T->m[s]; a.npts = T->npts[s];
-    a.c_keys = T->c_keys[s].as<int64_t>(); a.c_x = T->c_x[s].as<double>(); a.c_y = T->c_y[s].as<double>();
-    a.c_ts = T->c_ts[s].as<int64_t>(); a.c_idx = T->c_idx[s].as<uint32_t>();
-    GF_HIP_CHECK(ctx, launch_tjoin(ctx, 13, a));
+    a.c_keys = T->c_keys[s].p; a.c_x = T->c_x[s].p; a.c_y = T->c_y[s].p; a.c_ts = T->c_ts[s].p; a.c_idx = T->c_idx[s].p;
+    GF_HIP_CHECK(ctx, launch_tjoin(ctx, kTjoinGather, a));
   }
   GF_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return GF_OK;
@@ -292,8 +276,6 @@ extern "C" void gf_tjoin_destroy(gf_tjoin* T) {
     hipSetDevice(T->ctx->device);
     hipStreamSynchronize(T->ctx->stream);
   }
-  T->srt.release_groups();
-  for (DevBuf* b : T->all()) b->release();
   delete T;
 }
 
@@ -346,14 +328,12 @@ extern "C" int gf_tjoin_read_trajs(gf_tjoin* T, int side, int64_t* keys, int64_t
   int st = bind(ctx);
   if (st) return st;
   const size_t wt = (size_t)std::min(T->m[side], cap_traj), wp = (size_t)std::min(T->npts[side], cap_pts);
-  std::vector<uint32_t> ho;
-  if (off) ho.resize(wt + 1);
-  if ((st = read_back(ctx, keys, T->c_keys[side].p, wt)) ||
-      (st = read_back(ctx, off ? ho.data() : nullptr, T->toff[side].p, ho.size())) ||
+  OffsetRead ho;
+  if ((st = read_back(ctx, keys, T->c_keys[side].p, wt)) || (st = read_offsets(ctx, ho, off, T->toff[side].p, wt + 1)) ||
       (st = read_back(ctx, x, T->c_x[side].p, wp)) || (st = read_back(ctx, y, T->c_y[side].p, wp)) ||
       (st = read_back(ctx, ts, T->c_ts[side].p, wp)) || (st = read_back(ctx, idx, T->c_idx[side].p, wp)))
     return st;
   GF_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  for (size_t i = 0; i < ho.size(); ++i) off[i] = (int64_t)ho[i];
+  ho.widen();
   return GF_OK;
 }

@@ -2,8 +2,8 @@
 // windowBasedNaive, TKNNQuery.java:50-101): gf_tknn_run over a window already grouped by objID
 // (gf_traj_group), the read and the testing hook.  The kernels are in k_tknn.hip; the groupings by
 // cell and by (cell, trajectory), the sort of the pairs by cell and the multi-word sorts are
-// gf_group.hpp's (traj.cpp), run on k_points.hip's radix passes.  The object owns its device workspace (grow-only)
-// and is reused across windows.
+// gf_group.hpp's (traj.cpp), run on k_points.hip's radix passes.  The object is made of gf_group.hpp's
+// typed device arrays (grow-only, freed by its destructor) and is reused across windows.
 #define GF_TU_NAME tknn_cpp
 #include "gf_buildtag.hpp"  // first: records this unit's command-line defines
 
@@ -24,25 +24,13 @@ struct gf_tknn {
   KeyGroups cells, pairs;  // dense ids of the entries' packed cells and of their (cell, trajectory) keys
   KeyGroups bycell;        // the pairs sorted by cell id (sort only)
   KeyGroups srt;           // the multi-word sorts' radix workspace
-  DevBuf e_ckey, e_t, e_d, e_i, comp, counters, p_first, p_d, p_cell, p_rec, wkey, sp[2], tr_D, tr_cells, surv, srank,
-      slist, o_key, o_dist, o_cells, o_traj, o_len, o_off, o_x, o_y, o_ts, o_idx;
-  DevBuf* all[30] = {&e_ckey, &e_t, &e_d, &e_i, &comp, &counters, &p_first, &p_d, &p_cell, &p_rec, &wkey, &sp[0], &sp[1],
-                     &tr_D, &tr_cells, &surv, &srank, &slist, &o_key, &o_dist, &o_cells, &o_traj, &o_len, &o_off, &o_x,
-                     &o_y, &o_ts, &o_idx, nullptr, nullptr};
+  DevArr<int64_t> e_ckey, comp, o_key, o_ts;
+  DevArr<unsigned long long> e_d, p_d, tr_D;
+  DevArr<uint32_t> e_t, e_i, counters, p_first, p_cell, p_rec, wkey, sp[2], tr_cells, surv, srank, slist, o_traj, o_len,
+      o_off, o_idx;
+  DevArr<double> o_dist, o_x, o_y;
+  DevArr<int32_t> o_cells;
 };
-
-template <class T>
-static int read_back(gf_ctx* ctx, T* host, const void* dev, size_t count) {
-  if (!host || count == 0) return GF_OK;
-  GF_HIP_CHECK(ctx, hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-  return GF_OK;
-}
-
-static int key_bits(uint64_t nids) {
-  int bits = 1;
-  while (((uint64_t)1 << bits) < nids) ++bits;
-  return bits;
-}
 
 static int tknn_window(gf_tknn* T, gf_traj_groups* G, const gf_grid* grid, const gf_points* pts, double qx, double qy,
                        int32_t xlo, int32_t xhi, int32_t ylo, int32_t yhi, int32_t k, int naive) {
@@ -50,23 +38,21 @@ static int tknn_window(gf_tknn* T, gf_traj_groups* G, const gf_grid* grid, const
   int st = GF_OK;
   const int64_t n = G->n, nt = G->ntraj;
   const size_t np = (size_t)n, ntz = (size_t)nt;
-  if ((st = T->e_ckey.reserve(ctx, np * 8)) || (st = T->e_t.reserve(ctx, np * 4)) || (st = T->e_d.reserve(ctx, np * 8)) ||
-      (st = T->e_i.reserve(ctx, np * 4)) || (st = T->counters.reserve(ctx, 16)))
+  if ((st = T->e_ckey.reserve(ctx, np)) || (st = T->e_t.reserve(ctx, np)) || (st = T->e_d.reserve(ctx, np)) ||
+      (st = T->e_i.reserve(ctx, np)) || (st = T->counters.reserve(ctx, kCounterWords)))
     return st;
   TknnArgs a{};
   a.x = pts->x; a.y = pts->y; a.ts = pts->ts;
-  a.did = G->did.as<uint32_t>();
+  a.did = G->did.p;
   a.n = n;
   a.minX = grid->minX; a.minY = grid->minY; a.cl = grid->cellLength;
   a.qx = qx; a.qy = qy;
   a.xlo = xlo; a.xhi = xhi; a.ylo = ylo; a.yhi = yhi;
   a.naive = naive;
   a.k = k;
-  a.e_ckey = T->e_ckey.as<int64_t>(); a.e_t = T->e_t.as<uint32_t>();
-  a.e_d = T->e_d.as<unsigned long long>(); a.e_i = T->e_i.as<uint32_t>();
-  a.counters = T->counters.as<uint32_t>();
-  GF_HIP_CHECK(ctx, hipMemsetAsync(a.counters, 0, 16, ctx->stream));
-  GF_HIP_CHECK(ctx, launch_tknn(ctx, 0, a));
+  a.e_ckey = T->e_ckey.p; a.e_t = T->e_t.p; a.e_d = T->e_d.p; a.e_i = T->e_i.p; a.counters = T->counters.p;
+  GF_HIP_CHECK(ctx, hipMemsetAsync(a.counters, 0, kCounterWords * sizeof(uint32_t), ctx->stream));
+  GF_HIP_CHECK(ctx, launch_tknn(ctx, kTknnScanWindow, a));
   uint32_t m32 = 0;
   if ((st = read_scalar_sync(ctx, a.counters, &m32))) return st;
   const int64_t m = m32;
@@ -76,32 +62,30 @@ static int tknn_window(gf_tknn* T, gf_traj_groups* G, const gf_grid* grid, const
   a.m = m;
   // the entries' cells and (cell, trajectory) pairs
   if ((st = group_dense_ids(ctx, T->cells, a.e_ckey, m, "gf_tknn_run"))) return st;
-  if ((st = T->comp.reserve(ctx, (size_t)m * 8))) return st;
-  a.cid = T->cells.did.as<uint32_t>();
-  a.comp = T->comp.as<int64_t>();
-  GF_HIP_CHECK(ctx, launch_tknn(ctx, 1, a));
+  if ((st = T->comp.reserve(ctx, (size_t)m))) return st;
+  a.cid = T->cells.did.p;
+  a.comp = T->comp.p;
+  GF_HIP_CHECK(ctx, launch_tknn(ctx, kTknnCompose, a));
   if ((st = group_dense_ids(ctx, T->pairs, a.comp, m, "gf_tknn_run"))) return st;
   const int64_t npairs = T->pairs.ngroups, ncells = T->cells.ngroups;
   T->npairs = npairs;
   const size_t nq = (size_t)npairs;
-  if ((st = T->p_first.reserve(ctx, nq * 4)) || (st = T->p_d.reserve(ctx, nq * 8)) || (st = T->p_cell.reserve(ctx, nq * 4)) ||
-      (st = T->p_rec.reserve(ctx, nq * 4)) || (st = T->tr_D.reserve(ctx, ntz * 8)) ||
-      (st = T->tr_cells.reserve(ctx, ntz * 4)) || (st = T->surv.reserve(ctx, (ntz + 1) * 4)) ||
-      (st = T->srank.reserve(ctx, (ntz + 1) * 4)) || (st = T->slist.reserve(ctx, ntz * 4)))
+  if ((st = T->p_first.reserve(ctx, nq)) || (st = T->p_d.reserve(ctx, nq)) || (st = T->p_cell.reserve(ctx, nq)) ||
+      (st = T->p_rec.reserve(ctx, nq)) || (st = T->tr_D.reserve(ctx, ntz)) || (st = T->tr_cells.reserve(ctx, ntz)) ||
+      (st = T->surv.reserve(ctx, ntz + 1)) || (st = T->srank.reserve(ctx, ntz + 1)) || (st = T->slist.reserve(ctx, ntz)))
     return st;
-  a.pid = T->pairs.did.as<uint32_t>();
+  a.pid = T->pairs.did.p;
   a.npairs = npairs;
-  a.pkeys = T->pairs.keys.as<int64_t>();
-  a.p_first = T->p_first.as<uint32_t>(); a.p_d = T->p_d.as<unsigned long long>();
-  a.p_cell = T->p_cell.as<uint32_t>(); a.p_rec = T->p_rec.as<uint32_t>();
-  GF_HIP_CHECK(ctx, launch_tknn(ctx, 2, a));
+  a.pkeys = T->pairs.keys.p;
+  a.p_first = T->p_first.p; a.p_d = T->p_d.p; a.p_cell = T->p_cell.p; a.p_rec = T->p_rec.p;
+  GF_HIP_CHECK(ctx, launch_tknn(ctx, kTknnPairMin, a));
   // the cells' lists: pairs sorted stably by cell id (every cell has a pair)
   if ((st = group_sort_ids(ctx, T->bycell, a.p_cell, npairs, (uint32_t)ncells))) return st;
-  a.gperm = T->bycell.perm.as<uint32_t>();
-  a.gcell = T->bycell.kbuf[T->bycell.sorted_in].as<uint32_t>();
-  a.cell_off = T->bycell.seg_off.as<uint32_t>();
+  a.gperm = T->bycell.perm.p;
+  a.gcell = T->bycell.kbuf[T->bycell.sorted_in].p;
+  a.cell_off = T->bycell.seg_off.p;
   a.big_cell = (uint32_t)T->big_cell;
-  GF_HIP_CHECK(ctx, launch_tknn(ctx, 3, a));
+  GF_HIP_CHECK(ctx, launch_tknn(ctx, kTknnRankSmall, a));
   uint32_t nbig = 0;
   if ((st = read_scalar_sync(ctx, a.counters + 1, &nbig))) return st;
   if (nbig > 0) {
@@ -111,19 +95,18 @@ static int tknn_window(gf_tknn* T, gf_traj_groups* G, const gf_grid* grid, const
                                {a.p_d, nullptr, 32, 32},
                                {pk, nullptr, 32, key_bits((uint64_t)ncells)}};
     if ((st = group_sort_words(ctx, T->srt, T->wkey, T->sp, words, 4, npairs, nullptr, &a.sperm))) return st;
-    GF_HIP_CHECK(ctx, launch_tknn(ctx, 4, a));
+    GF_HIP_CHECK(ctx, launch_tknn(ctx, kTknnRankBig, a));
   }
   // per trajectory: D_t, cells_t, the size rule
   a.ntraj = nt;
-  a.seg_off = G->seg_off.as<uint32_t>();
-  a.tr_D = T->tr_D.as<unsigned long long>(); a.tr_cells = T->tr_cells.as<uint32_t>();
-  a.surv = T->surv.as<uint32_t>(); a.srank = T->srank.as<uint32_t>(); a.slist = T->slist.as<uint32_t>();
-  GF_HIP_CHECK(ctx, launch_tknn(ctx, 5, a));
-  if ((st = group_scan_u32(ctx, T->srt, a.surv, nt, T->srank.as<uint32_t>()))) return st;
-  GF_HIP_CHECK(ctx, launch_tknn(ctx, 6, a));
+  a.seg_off = G->seg_off.p;
+  a.tr_D = T->tr_D.p; a.tr_cells = T->tr_cells.p; a.surv = T->surv.p; a.srank = T->srank.p; a.slist = T->slist.p;
+  GF_HIP_CHECK(ctx, launch_tknn(ctx, kTknnCombine, a));
+  if ((st = group_scan_u32(ctx, T->srt, a.surv, nt, T->srank.p))) return st;
+  GF_HIP_CHECK(ctx, launch_tknn(ctx, kTknnSurvivors, a));
   uint32_t tot[4] = {0, 0, 0, 0};  // survivors, -, records
-  GF_HIP_CHECK(ctx, hipMemcpyAsync(&tot[0], a.srank + nt, 4, hipMemcpyDeviceToHost, ctx->stream));
-  GF_HIP_CHECK(ctx, hipMemcpyAsync(&tot[2], a.counters + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
+  GF_HIP_CHECK(ctx, hipMemcpyAsync(&tot[0], a.srank + nt, sizeof tot[0], hipMemcpyDeviceToHost, ctx->stream));
+  GF_HIP_CHECK(ctx, hipMemcpyAsync(&tot[2], a.counters + 2, sizeof tot[2], hipMemcpyDeviceToHost, ctx->stream));
   GF_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   T->records = tot[2];
   const int64_t nsurv = tot[0];
@@ -134,27 +117,26 @@ static int tknn_window(gf_tknn* T, gf_traj_groups* G, const gf_grid* grid, const
   if ((st = group_sort_words(ctx, T->srt, T->wkey, T->sp, dw, 2, nsurv, nullptr, &a.order))) return st;
   const int64_t rows = std::min<int64_t>(nsurv, k);
   const size_t nr = (size_t)rows;
-  if ((st = T->o_key.reserve(ctx, nr * 8)) || (st = T->o_dist.reserve(ctx, nr * 8)) || (st = T->o_cells.reserve(ctx, nr * 4)) ||
-      (st = T->o_traj.reserve(ctx, nr * 4)) || (st = T->o_len.reserve(ctx, (nr + 1) * 4)) ||
-      (st = T->o_off.reserve(ctx, (nr + 1) * 4)))
+  if ((st = T->o_key.reserve(ctx, nr)) || (st = T->o_dist.reserve(ctx, nr)) || (st = T->o_cells.reserve(ctx, nr)) ||
+      (st = T->o_traj.reserve(ctx, nr)) || (st = T->o_len.reserve(ctx, nr + 1)) || (st = T->o_off.reserve(ctx, nr + 1)))
     return st;
   a.rows = rows;
-  a.tkeys = G->keys.as<int64_t>();
-  a.perm = G->perm.as<uint32_t>();
-  a.o_key = T->o_key.as<int64_t>(); a.o_dist = T->o_dist.as<double>(); a.o_cells = T->o_cells.as<int32_t>();
-  a.o_traj = T->o_traj.as<uint32_t>(); a.o_len = T->o_len.as<uint32_t>(); a.o_off = T->o_off.as<uint32_t>();
-  GF_HIP_CHECK(ctx, launch_tknn(ctx, 7, a));
-  if ((st = group_scan_u32(ctx, T->srt, a.o_len, rows, T->o_off.as<uint32_t>()))) return st;
+  a.tkeys = G->keys.p;
+  a.perm = G->perm.p;
+  a.o_key = T->o_key.p; a.o_dist = T->o_dist.p; a.o_cells = T->o_cells.p; a.o_traj = T->o_traj.p; a.o_len = T->o_len.p;
+  a.o_off = T->o_off.p;
+  GF_HIP_CHECK(ctx, launch_tknn(ctx, kTknnRows, a));
+  if ((st = group_scan_u32(ctx, T->srt, a.o_len, rows, T->o_off.p))) return st;
   uint32_t npts = 0;
   if ((st = read_scalar_sync(ctx, a.o_off + rows, &npts))) return st;
   if ((int64_t)npts > n) return set_err(ctx, GF_ERR_HIP, "gf_tknn_run: inconsistent point count");
   const size_t no = (size_t)npts;
-  if ((st = T->o_x.reserve(ctx, no * 8)) || (st = T->o_y.reserve(ctx, no * 8)) || (st = T->o_ts.reserve(ctx, no * 8)) ||
-      (st = T->o_idx.reserve(ctx, no * 4)))
+  if ((st = T->o_x.reserve(ctx, no)) || (st = T->o_y.reserve(ctx, no)) || (st = T->o_ts.reserve(ctx, no)) ||
+      (st = T->o_idx.reserve(ctx, no)))
     return st;
   a.npts = npts;
-  a.o_x = T->o_x.as<double>(); a.o_y = T->o_y.as<double>(); a.o_ts = T->o_ts.as<int64_t>(); a.o_idx = T->o_idx.as<uint32_t>();
-  GF_HIP_CHECK(ctx, launch_tknn(ctx, 8, a));
+  a.o_x = T->o_x.p; a.o_y = T->o_y.p; a.o_ts = T->o_ts.p; a.o_idx = T->o_idx.p;
+  GF_HIP_CHECK(ctx, launch_tknn(ctx, kTknnGather, a));
   GF_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   T->rows = rows;
   T->npts = npts;
@@ -209,11 +191,6 @@ extern "C" void gf_tknn_destroy(gf_tknn* T) {
     hipSetDevice(T->ctx->device);
     hipStreamSynchronize(T->ctx->stream);
   }
-  T->cells.release_groups();
-  T->pairs.release_groups();
-  T->bycell.release_groups();
-  T->srt.release_groups();
-  for (DevBuf** b = T->all; *b; ++b) (*b)->release();
   delete T;
 }
 
@@ -244,14 +221,13 @@ extern "C" int gf_tknn_read(gf_tknn* T, int64_t* keys, double* dist, int32_t* ce
   int st = bind(ctx);
   if (st) return st;
   const size_t wr = (size_t)std::min(T->rows, cap_rows), wp = (size_t)std::min(T->npts, cap_pts);
-  std::vector<uint32_t> ho;
-  if (off) ho.resize(wr + 1);
+  OffsetRead ho;
   if ((st = read_back(ctx, keys, T->o_key.p, wr)) || (st = read_back(ctx, dist, T->o_dist.p, wr)) ||
-      (st = read_back(ctx, cells, T->o_cells.p, wr)) || (st = read_back(ctx, off ? ho.data() : nullptr, T->o_off.p, ho.size())) ||
+      (st = read_back(ctx, cells, T->o_cells.p, wr)) || (st = read_offsets(ctx, ho, off, T->o_off.p, wr + 1)) ||
       (st = read_back(ctx, x, T->o_x.p, wp)) || (st = read_back(ctx, y, T->o_y.p, wp)) ||
       (st = read_back(ctx, ts, T->o_ts.p, wp)) || (st = read_back(ctx, idx, T->o_idx.p, wp)))
     return st;
   GF_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  for (size_t i = 0; i < ho.size(); ++i) off[i] = (int64_t)ho[i];
+  ho.widen();
   return GF_OK;
 }

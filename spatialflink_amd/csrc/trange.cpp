@@ -2,8 +2,8 @@
 // once per continuous query (its pure host part is gf_trange_plan.hpp's), gf_trange_points (RealTime:
 // the contained points' bitmap, enqueued) and gf_trange_run (WindowBased: the trajectories with a
 // contained point, each whole; the CSR is traj.cpp's traj_emit, shared with gf_traj_select and
-// gf_tfilter_run).  The kernels are in k_trange.hip.  The plan owns its device tables and the wave
-// path's worklist (grow-only).
+// gf_tfilter_run).  The kernels are in k_trange.hip.  The plan's device tables and the wave path's
+// worklist (grow-only) are gf_group.hpp's typed device arrays, freed by its destructor.
 #define GF_TU_NAME trange_cpp
 #include "gf_buildtag.hpp"  // first: records this unit's command-line defines
 
@@ -23,12 +23,11 @@ struct gf_trange_plan {
   int64_t max_wide = 0;  // the most wide candidates any one point can have
   int64_t cell_points = 0, inside_points = 0;
   int wave_path = 0;  // the last gf_trange_points / gf_trange_run tested its wide polygons by waves
-  uint8_t* cls = nullptr;
-  int32_t *cand_off = nullptr, *cand_list = nullptr, *extra = nullptr, *ring_off = nullptr, *vert_off = nullptr;
-  double *vx = nullptr, *vy = nullptr, *ring_env = nullptr;
-  uint8_t* wide = nullptr;
-  unsigned long long* ctr = nullptr;
-  DevBuf work;
+  DevArr<uint8_t> cls, wide;
+  DevArr<int32_t> cand_off, cand_list, extra, ring_off, vert_off;
+  DevArr<double> vx, vy, ring_env;
+  DevArr<unsigned long long> ctr;
+  DevArr<uint2> work;
 };
 
 // the worklist never outgrows this: a window whose bound is larger tests every polygon by its lane
@@ -55,7 +54,7 @@ static int trange_apply_wide(gf_trange_plan* P) {
   for (size_t e = 0; e < T.extra.size(); e += 5) ex += w[T.extra[e]];
   P->max_wide = std::max(mx, ex);
   GF_HIP_CHECK(P->ctx, hipStreamSynchronize(P->ctx->stream));  // queued work may still read the flags
-  GF_HIP_CHECK(P->ctx, hipMemcpy(P->wide, w.data(), w.size(), hipMemcpyHostToDevice));
+  GF_HIP_CHECK(P->ctx, hipMemcpy(P->wide.p, w.data(), w.size(), hipMemcpyHostToDevice));
   return GF_OK;
 }
 
@@ -63,11 +62,6 @@ extern "C" void gf_trange_plan_destroy(gf_trange_plan* P) {
   if (!P) return;
   hipSetDevice(P->ctx->device);
   hipStreamSynchronize(P->ctx->stream);
-  void* bufs[] = {P->cls, P->cand_off, P->cand_list, P->extra, P->ring_off, P->vert_off, P->vx, P->vy, P->ring_env,
-                  P->wide, P->ctr};
-  for (void* b : bufs)
-    if (b) hipFree(b);
-  P->work.release();
   delete P;
 }
 
@@ -98,11 +92,11 @@ extern "C" int gf_trange_plan_create(gf_ctx* ctx, const gf_grid* g, const gf_pol
   std::vector<double> vx(polys->vx, polys->vx + nverts), vy(polys->vy, polys->vy + nverts);
   std::vector<uint8_t> w((size_t)std::max(np, 1), 0);
   std::vector<unsigned long long> zero(4, 0);
-  if ((st = upload(ctx, &P->cls, T.cls)) || (st = upload(ctx, &P->cand_off, T.cand_off)) ||
-      (st = upload(ctx, &P->cand_list, T.cand_list)) || (st = upload(ctx, &P->extra, T.extra)) ||
-      (st = upload(ctx, &P->ring_off, ro)) || (st = upload(ctx, &P->vert_off, vo)) || (st = upload(ctx, &P->vx, vx)) ||
-      (st = upload(ctx, &P->vy, vy)) || (st = upload(ctx, &P->ring_env, T.ring_env)) || (st = upload(ctx, &P->wide, w)) ||
-      (st = upload(ctx, &P->ctr, zero)) || (st = trange_apply_wide(P))) {
+  if ((st = upload(ctx, P->cls, T.cls)) || (st = upload(ctx, P->cand_off, T.cand_off)) ||
+      (st = upload(ctx, P->cand_list, T.cand_list)) || (st = upload(ctx, P->extra, T.extra)) ||
+      (st = upload(ctx, P->ring_off, ro)) || (st = upload(ctx, P->vert_off, vo)) || (st = upload(ctx, P->vx, vx)) ||
+      (st = upload(ctx, P->vy, vy)) || (st = upload(ctx, P->ring_env, T.ring_env)) || (st = upload(ctx, P->wide, w)) ||
+      (st = upload(ctx, P->ctr, zero)) || (st = trange_apply_wide(P))) {
     gf_trange_plan_destroy(P);
     return st;
   }
@@ -144,20 +138,20 @@ static int trange_args(gf_trange_plan* P, const gf_points* pts, TrangeArgs& a) {
   gf_ctx* ctx = P->ctx;
   a.x = pts->x; a.y = pts->y; a.n = pts->n;
   a.grid_n = P->grid.n; a.minX = P->grid.minX; a.minY = P->grid.minY; a.cl = P->grid.cellLength;
-  a.cls = P->cls; a.cand_off = P->cand_off; a.cand_list = P->cand_list;
-  a.extra = P->extra; a.n_extra = (int32_t)(P->tab.extra.size() / 5);
-  a.poly.ring_off = P->ring_off; a.poly.vert_off = P->vert_off; a.poly.vx = P->vx; a.poly.vy = P->vy;
-  a.poly.ring_env = P->ring_env; a.poly.metric = 0; a.poly.rect = nullptr;
-  a.ctr = P->ctr;
+  a.cls = P->cls.p; a.cand_off = P->cand_off.p; a.cand_list = P->cand_list.p;
+  a.extra = P->extra.p; a.n_extra = (int32_t)(P->tab.extra.size() / 5);
+  a.poly.ring_off = P->ring_off.p; a.poly.vert_off = P->vert_off.p; a.poly.vx = P->vx.p; a.poly.vy = P->vy.p;
+  a.poly.ring_env = P->ring_env.p; a.poly.metric = 0; a.poly.rect = nullptr;
+  a.ctr = P->ctr.p;
   a.wide = nullptr;
   a.work = nullptr;
   a.work_cap = 0;
   P->wave_path = 0;
   if (P->max_wide > 0 && (size_t)P->max_wide <= kTrangeMaxWorkBytes / sizeof(uint2) / (size_t)pts->n) {
     const size_t cap = (size_t)P->max_wide * (size_t)pts->n;
-    if (int st = P->work.reserve(ctx, cap * sizeof(uint2))) return st;
-    a.wide = P->wide;
-    a.work = P->work.as<uint2>();
+    if (int st = P->work.reserve(ctx, cap)) return st;
+    a.wide = P->wide.p;
+    a.work = P->work.p;
     a.work_cap = (uint32_t)cap;
     P->wave_path = 1;
   }
@@ -180,9 +174,9 @@ extern "C" int gf_trange_points(gf_trange_plan* P, const gf_points* pts, uint64_
   if ((st = trange_args(P, pts, a))) return st;
   a.bitmap = bitmap;
   a.count = count;
-  GF_HIP_CHECK(ctx, launch_trange(ctx, 0, a));
-  if (a.wide) GF_HIP_CHECK(ctx, launch_trange(ctx, 1, a));
-  if (count) GF_HIP_CHECK(ctx, launch_trange(ctx, 2, a));
+  GF_HIP_CHECK(ctx, launch_trange(ctx, kTrangeMark, a));
+  if (a.wide) GF_HIP_CHECK(ctx, launch_trange(ctx, kTrangeWaves, a));
+  if (count) GF_HIP_CHECK(ctx, launch_trange(ctx, kTrangeCount, a));
   return GF_OK;
 }
 
@@ -203,10 +197,10 @@ extern "C" int gf_trange_run(gf_trange_plan* P, gf_traj_groups* G, const gf_poin
   if ((st = bind(ctx)) || (st = traj_hit_clear(G))) return st;
   TrangeArgs a{};
   if ((st = trange_args(P, pts, a))) return st;
-  a.did = G->did.as<uint32_t>();
-  a.hit = G->hit.as<uint32_t>();
-  GF_HIP_CHECK(ctx, launch_trange(ctx, 0, a));
-  if (a.wide) GF_HIP_CHECK(ctx, launch_trange(ctx, 1, a));
+  a.did = G->did.p;
+  a.hit = G->hit.p;
+  GF_HIP_CHECK(ctx, launch_trange(ctx, kTrangeMark, a));
+  if (a.wide) GF_HIP_CHECK(ctx, launch_trange(ctx, kTrangeWaves, a));
   // the counters ride to pinned staging behind the kernels; the emit's synchronisation completes the copy
   unsigned long long* c = (unsigned long long*)ctx_pinned(ctx, 4 * sizeof(unsigned long long), &st);
   if (!c) return st;
