@@ -150,6 +150,11 @@ extern "C" int gf_knn_sliding_push(gf_knn_sliding* s, int64_t pane_index, const 
     return set_err(ctx, GF_ERR_ARG, "gf_knn_sliding_push: panes must be pushed consecutively (empty panes with n = 0)");
   if (pane->n < 0) return set_err(ctx, GF_ERR_ARG, "gf_knn_sliding_push: negative n");
   if (P->pipeline > 2) return set_err(ctx, GF_ERR_ARG, "gf_knn_sliding_push: the pane engine runs at pipeline depth <= 2");
+  // the window this pane closes (if any) fires iff the pane or an earlier pane of it holds a point (the
+  // pane's own slot still holds pane_index - R, which window_has_points skips): refused with nothing
+  // enqueued and no state changed, so the caller can push the same pane again with a record
+  const bool fires = closes_window(s, pane_index) && (pane->n > 0 || window_has_points(s, pane_index));
+  if (fires && !window_result) return set_err(ctx, GF_ERR_ARG, "gf_knn_sliding_push: a window closes, result is null");
   int st = bind(ctx);
   if (st) return st;
   gf_knn_sliding::Pane& pn = slot(s, pane_index);
@@ -176,8 +181,7 @@ extern "C" int gf_knn_sliding_push(gf_knn_sliding* s, int64_t pane_index, const 
     s->pend = false;
     if (!merged && (st = merge_window(s, s->pend_last, s->pend_result))) return st;
   }
-  if (closes_window(s, pane_index) && window_has_points(s, pane_index)) {
-    if (!window_result) return set_err(ctx, GF_ERR_ARG, "gf_knn_sliding_push: a window closes, result is null");
+  if (fires) {
     *closed = 1;
     if (window_end) *window_end = (pane_index + 1) * s->pane_ms;
     if (knn_select_pending(P)) {

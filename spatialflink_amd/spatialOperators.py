@@ -81,7 +81,7 @@ class _PlanCache:
         self.limit = int(limit)
         self._d = OrderedDict()
         self._pinned = set()  # plans with state beyond their key (pipeline, capacity)
-        self._held = set()    # plans a pane engine (gf_*_sliding) borrows: never destroyed under it
+        self._held = {}       # plan -> number of pane engines (gf_*_sliding) borrowing it: never destroyed under them
         self._orphans = {}    # held plans of a closed cache: destroyed when their engine lets go
 
     def pin(self, plan):
@@ -97,14 +97,25 @@ class _PlanCache:
     def hold(self, plan):
         """A pane engine borrows `plan` (the engine dereferences it until it is destroyed): the
         plan is not evicted, and close() leaves its destruction to release() -- the operator and
-        the engine may be finalized in either order (both die in one collected cycle)."""
-        self._held.add(self._pv(plan))
+        the engine may be finalized in either order (both die in one collected cycle).  Holds
+        count: engines sharing one plan (two range engines on one query) each hold it, and it stays
+        until the last of them lets go."""
+        pv = self._pv(plan)
+        self._held[pv] = self._held.get(pv, 0) + 1
+
+    def holds(self, plan) -> int:
+        """Number of pane engines borrowing `plan`."""
+        return self._held.get(self._pv(plan), 0)
 
     def release(self, plan):
-        """The pane engine is destroyed: the plan is an ordinary LRU entry again, or, if the cache
-        closed meanwhile, destroyed now."""
+        """A pane engine is destroyed: once no engine holds the plan it is an ordinary LRU entry
+        again, or, if the cache closed meanwhile, destroyed now."""
         pv = self._pv(plan)
-        self._held.discard(pv)
+        n = self._held.get(pv, 0)
+        if n > 1:
+            self._held[pv] = n - 1
+            return
+        self._held.pop(pv, None)
         orphan = self._orphans.pop(pv, None)
         if orphan is not None:
             self._destroy(orphan)

@@ -161,12 +161,21 @@ class SlidingKNNQuery:
         # queryPoint is then its query geometry); default the point query
         self.op = op if op is not None else PointPointKNNQuery(conf, grid)
         self.ctx, self.plan = self.op.plan(device, queryPoint, queryRadius, k)
+        # the plan carries this engine's idx_base, pipeline depth and pending-select queue: two live
+        # engines on one plan would overwrite each other's (range plans are stateless and may be shared)
+        if self.op._plans.holds(self.plan):
+            raise ValueError("another live SlidingKNNQuery already runs on this operator's plan for the same "
+                             "(query, radius, k): give each sliding kNN engine a separate operator")
         self.op._plans.hold(self.plan)  # the pane engine borrows it
         self.depth = int(pipeline)  # k > 256: the select is not fused, records complete in stream order
-        _lib.check(_lib.lib().gf_knn_plan_set_pipeline(self.plan, self.depth), self.ctx.handle, "set_pipeline")
         h = C.c_void_p()
-        _lib.check(_lib.lib().gf_knn_sliding_create(self.plan, self.geo.size, self.geo.slide, C.byref(h)),
-                   self.ctx.handle, "gf_knn_sliding_create")
+        try:
+            _lib.check(_lib.lib().gf_knn_plan_set_pipeline(self.plan, self.depth), self.ctx.handle, "set_pipeline")
+            _lib.check(_lib.lib().gf_knn_sliding_create(self.plan, self.geo.size, self.geo.slide, C.byref(h)),
+                       self.ctx.handle, "gf_knn_sliding_create")
+        except Exception:
+            self.op._plans.release(self.plan)  # a refused engine borrows nothing
+            raise
         self.handle = h
         ring = C.c_int32()
         _lib.check(_lib.lib().gf_knn_sliding_geometry(h, None, None, None, C.byref(ring)), self.ctx.handle, "geometry")
@@ -294,11 +303,11 @@ class SlidingRangeQuery:
 
         if self.handle is None:
             self.ctx, plan = self.op.plan(device, self.queries, self.r)
-            self.op._plans.hold(plan)
-            self.plan = plan
             h = C.c_void_p()
             _lib.check(_lib.lib().gf_range_sliding_create(plan, self.geo.size, self.geo.slide, C.byref(h)),
                        self.ctx.handle, "gf_range_sliding_create")
+            self.op._plans.hold(plan)  # range plans are stateless: engines may share one, each holds it
+            self.plan = plan
             self.handle = h
             self._spare = torch.empty(1, dtype=torch.int32, device=f"cuda:{self.ctx.device}")
         return self.handle

@@ -123,3 +123,72 @@ def test_plan_cache_never_evicts_the_inserted_plan(monkeypatch):
     c.unpin(100)  # released pin: the oldest unpinned entries go until the limit holds
     assert destroyed == [200, 100] and len(c) == 3
     assert c.get("e") == 201 and c.get("b") == 101 and c.get("c") == 102
+
+
+def test_plan_cache_counts_holds(monkeypatch):
+    """Two pane engines on one operator and one query share the cached plan (two SlidingRangeQuery at
+    two window sizes): each holds it, and the plan is neither evicted nor destroyed until the LAST of
+    them lets go -- then exactly once.  (A set of held plans lost the second hold: the first engine's
+    release() made the plan evictable under the second engine.)"""
+    from spatialflink_amd import spatialOperators as so
+
+    destroyed = []
+    monkeypatch.setattr(so._PlanCache, "_destroy", lambda self, p: destroyed.append(p))
+    # hold twice, release once: the plan survives eviction ...
+    c = so._PlanCache("unused", limit=1)
+    c.put("a", 101)
+    c.hold(101)
+    c.hold(101)
+    assert c.holds(101) == 2
+    c.release(101)
+    assert c.holds(101) == 1
+    c.put("b", 102)
+    c.put("c", 103)
+    assert destroyed == [102] and c.get("a") == 101
+    # ... and close()
+    c.close()
+    assert destroyed == [102, 103] and len(c) == 0
+    # the second release destroys it, exactly once
+    c.release(101)
+    assert destroyed == [102, 103, 101] and c.holds(101) == 0
+    c.release(101)
+    assert destroyed == [102, 103, 101]
+    # the engines go first: the plan is an LRU entry again only after the last release
+    c = so._PlanCache("unused", limit=1)
+    c.put("a", 201)
+    c.hold(201)
+    c.hold(201)
+    c.put("b", 202)
+    c.release(201)
+    assert destroyed[3:] == [] and c.get("a") == 201
+    c.get("b")
+    c.release(201)
+    assert destroyed[3:] == [201] and c.get("b") == 202
+    c.close()
+    assert destroyed[3:] == [201, 202]
+
+
+def test_sliding_knn_refuses_a_shared_plan(monkeypatch):
+    """A kNN plan carries its engine's idx_base, pipeline depth and pending-select queue, so a second
+    live SlidingKNNQuery on an operator whose plan for that (query, r, k) is held is refused before any
+    device call, naming the remedy; the first engine's hold is untouched."""
+    import spatialflink_amd as sf
+    from spatialflink_amd import spatialOperators as so
+    from spatialflink_amd.windows import SlidingKNNQuery
+
+    destroyed = []
+    monkeypatch.setattr(so._PlanCache, "_destroy", lambda self, p: destroyed.append(p))
+
+    class Op:
+        _plans = so._PlanCache("unused")
+
+        def plan(self, device, q, r, k):
+            return object(), 101
+
+    op = Op()
+    op._plans.put("a", 101)
+    op._plans.hold(101)  # a live engine
+    conf = sf.QueryConfiguration(sf.QueryType.WindowBased)
+    with pytest.raises(ValueError, match="separate operator"):
+        SlidingKNNQuery(conf, None, None, 0.5, 5, size_ms=3000, slide_ms=1000, op=op)
+    assert op._plans.holds(101) == 1 and destroyed == []
