@@ -67,7 +67,8 @@ extern "C" {
 #define GF_K_TKNN        16 /* tKnn: its own kernels (the grouping kernels count as GF_K_TRAJ_GROUP, the radix passes as GF_K_BUCKET) */
 #define GF_K_TJOIN       17 /* tJoin: its own kernels (the radix passes count as GF_K_BUCKET) */
 #define GF_K_TRANGE      18 /* tRange: the contains pass (gf_trange_points / gf_trange_run; the emit counts as GF_K_TRAJ_SELECT) */
-#define GF_K_COUNT       19
+#define GF_K_GEOM        19 /* polygon / linestring windows: prepare, classify and the exact passes (the kNN select counts as GF_K_KNN_SELECT) */
+#define GF_K_COUNT       20
 
 typedef struct gf_ctx gf_ctx;
 
@@ -968,6 +969,110 @@ int  gf_trange_info(const gf_trange_plan* p, int64_t* cell_points, int64_t* insi
 int  gf_tfilter_run(gf_traj_groups* g, const gf_points* pts, const int64_t* id_set, int64_t nset, int64_t* keys,
                     int64_t* off, int64_t cap_traj, double* x, double* y, int64_t* ts, uint32_t* idx, int64_t cap_pts,
                     int64_t* ntraj_out, int64_t* npts_out);
+
+/* ---- polygon and linestring windows: range and kNN against query points ----------------------
+ * range/PolygonPointRangeQuery.java:116-196, range/LineStringPointRangeQuery.java:118-191,
+ * knn/PolygonPointKNNQuery.java:136-209, knn/LineStringPointKNNQuery.java:136-206 (WindowBased) with
+ * KNNQuery.kNNWinAllEvaluationPolygonStream: the WINDOW holds geometries, the query is a point set.
+ * The contract (derived from the reference and JTS 1.16.1, nothing was run on a JVM):
+ *  1. Window objects.  A window holds nobj objects of one kind (gf_geoms, device CSR).  A polygon is
+ *     its rings, ring 0 the shell, every ring closed with >= 4 vertices (as gf_polygons); a linestring
+ *     is an open chain of >= 2 vertices (as gf_linestrings).  boundingBox = the vertex envelope, for a
+ *     polygon its shell's (JTS).  gridIDsSet = HelperClass.assignGridCellID(bbox) (HelperClass.java:
+ *     123-143; holes are taken to lie inside the shell's envelope, as in a valid JTS polygon -- the
+ *     exact pass skips an object whose SHELL envelope is provably farther than r): the rectangle of cells [cx1..cx2] x [cy1..cy2] of the envelope's corners, each index
+ *     K1's floor with Java (int) saturation, NOT clamped to the grid.  A cell outside the grid belongs
+ *     to no neighbour set (UniformGrid.validKey).
+ *  2. Query side.  N = the union over the query points of getNeighboringCells(r, point): the valid
+ *     cells within L = getCandidateNeighboringLayers(r) layers of the point's cell (the point may lie
+ *     outside the grid: its cell index is used as it is, as the point plans do); r == 0: N = every
+ *     valid cell; r != 0 and L <= 0: GF_ERR_LAYERS (the reference's System.exit(1)).  G = the union of
+ *     getGuaranteedNeighboringCells(r, point.gridID): layers -1 -> nothing, 0 -> the point's cell,
+ *     g > 0 -> the valid cells within g layers.
+ *  3. Range.  An object passes the filter iff some cell of its rectangle is in N.  A filtered object
+ *     is emitted, once, iff (a) every cell of its rectangle is in G, or (b) not (a) and some query
+ *     point has d <= r.  The Java loop over the HashSet counts G cells and leaves at the first cell
+ *     outside G with the distance test, emitting at the last cell only when all were in G: the result
+ *     does not depend on the set's iteration order.  A rectangle that leaves the grid is never all-G.
+ *     Exact: d = DistanceFunctions.getDistance(point, polygon) -- the JTS point-polygon distance, 0
+ *     inside -- or getDistance(point, lineString), the open-chain minimum with no containment; either
+ *     metric.  Approximate: d = getPointPolygonBBoxMinEuclideanDistance /
+ *     getPointLineStringBBoxMinEuclideanDistance on the object's own envelope.
+ *  4. kNN.  One query point.  Candidates: the objects with a rectangle cell in N (G is not used) and
+ *     d <= r, d as in 3.  The record is the library's kNN record contract, not the reference's
+ *     arrival-order ties: entries sorted by (d, objID key, idx), one entry per objID key holding its
+ *     smallest d (among equal d the smallest idx), at most k entries, idx = the object's index in the
+ *     window.  The reference keys polygons by "" (one heap, then the dedupe of KNNQuery) and
+ *     linestrings by the matched cell (per-cell heaps, then the same merge): both collapse to this.
+ *     A plain gf_knn_header record, status always 0 (no hint, no fallback): gf_knn_merge_dev(_batch)
+ *     and record decoding take it unchanged.  k <= 512: the one-block select; larger k: the sorted path.
+ *  5. Errors, before any device call: a null handle or required pointer, nobj < 0, nq <= 0, k < 1, a
+ *     kNN query with nq != 1, a window prepared on another grid or context than the query's, a kind
+ *     other than the two, a bad metric, a grid of more than 46340 partitions (the summed-area tables
+ *     are int32): GF_ERR_ARG.  An empty window: an all-zero bitmap / a record with n = 0.
+ *  6. An object with a ring of fewer than 4 vertices, an unclosed ring, no ring at all, or a chain of
+ *     fewer than 2 vertices is never selected; gf_geom_prepare counts such objects (`invalid`).  The
+ *     reference leaves a null JTS object and throws later.  Non-finite vertex coordinates are outside
+ *     this contract.  The offset arrays are trusted to be monotone and in bounds, as gf_points.n is.
+ * Not covered: RealTime mode, Flink's triggers and sliding assignment, sharding across GPUs, JNI.
+ *
+ * gf_geoms: polygons -- object i owns rings [ring_off[i], ring_off[i+1]); ring j owns vertices
+ * [vert_off[j], vert_off[j+1]).  Linestrings -- ring_off == NULL, object i owns vertices
+ * [vert_off[i], vert_off[i+1]).  Every pointer is a DEVICE pointer.  vx / vy may be NULL only when the
+ * window holds no vertex at all (every object is then invalid).
+ * gf_geom_prepare (async; once per window, its index reusable by many queries of the same context and
+ * grid): per ring its envelope, per object its envelope, cell rectangle, validity and vertex count.
+ * *out == NULL: a new index; otherwise that index (of the same context) is prepared again for the new
+ * window -- its threshold kept, its device arrays reused and grow-only -- which is the per-window path of
+ * a continuous query.  Only launches are enqueued, with no host read (geoms->nrings carries the ring
+ * count); a new index, or a window with more objects or rings than the index has held, first synchronises
+ * the stream and allocates, as gf_trange_points does for its worklist.  The window's arrays are borrowed:
+ * they must stay valid and unchanged while the index is in use.
+ * One stream: an index holds the worklists of the run in flight and a query its counters and kNN
+ * candidates, so every call on an index or a query must be enqueued on the context stream (runs of
+ * several queries on one index are then ordered); running them from the streams gf_ctx_fork orders
+ * would race.
+ * Objects of at least wide_vertices vertices (gf_geom_index_set_thresholds; 0 = the default, 384; >= 1)
+ * are tested by one wave instead of one lane, and rings of at least as many have their envelope taken
+ * by one wave; results are identical for any value.  gf_geom_index_info (sync): objects, vertices,
+ * invalid objects, objects at or above the threshold.  gf_geom_index_read (sync, tests): env = x1, y1,
+ * x2, y2 per object; cells = cx1, cy1, cx2, cy2 per object.
+ * gf_geom_query_create (once per continuous query): the per-cell N / G tables of the point set and
+ * their summed-area tables, so "some cell in N" and "every cell in G" are two rectangle sums for any nq.
+ * gf_geom_range_run (async): bitmap = device uint64[(nobj+63)/64], gf_range_run's layout, every word
+ * written (gf_bitmap_to_indices(_async) take it); counts (nullable) = device int64[2]: objects
+ * emitted, and those emitted through rule 3(a).
+ * gf_geom_knn_enqueue (async): one record of gf_knn_result_bytes(k) into device memory `result`;
+ * needs geoms->objID.
+ * gf_geom_info (sync, of the query's last run): objects that passed the filter, those all-G, those
+ * whose distance was evaluated (the exact passes' worklists), and those of them tested by a wave. */
+#define GF_GEOM_POLYGON    1
+#define GF_GEOM_LINESTRING 2
+typedef struct {
+  int32_t kind;
+  int32_t nrings;        /* polygons: the rings of the window, ring_off[nobj] (trusted, as the offsets); linestrings: unused */
+  int64_t nobj;
+  const int32_t* ring_off;
+  const int32_t* vert_off;
+  const double* vx;
+  const double* vy;
+  const int64_t* objID;  /* objID keys; kNN only */
+  const int64_t* ts;     /* never read by window evaluation */
+} gf_geoms;
+typedef struct gf_geom_index gf_geom_index;
+int  gf_geom_prepare(gf_ctx* ctx, const gf_grid* g, const gf_geoms* geoms, gf_geom_index** out);
+void gf_geom_index_destroy(gf_geom_index* ix);
+int  gf_geom_index_info(gf_geom_index* ix, int64_t* nobj, int64_t* nvert, int64_t* invalid, int64_t* wide);
+int  gf_geom_index_read(gf_geom_index* ix, double* env, int32_t* cells);
+int  gf_geom_index_set_thresholds(gf_geom_index* ix, int32_t wide_vertices);
+typedef struct gf_geom_query gf_geom_query;
+int  gf_geom_query_create(gf_ctx* ctx, const gf_grid* g, const double* qx, const double* qy, int32_t nq, double r,
+                          int approximate, int metric, gf_geom_query** out);
+void gf_geom_query_destroy(gf_geom_query* q);
+int  gf_geom_range_run(gf_geom_query* q, gf_geom_index* ix, uint64_t* bitmap, int64_t* counts);
+int  gf_geom_knn_enqueue(gf_geom_query* q, gf_geom_index* ix, int32_t k, void* result);
+int  gf_geom_info(const gf_geom_query* q, int64_t* filtered, int64_t* all_guaranteed, int64_t* tested,
+                  int64_t* wave_path);
 
 /* ---- pinned host memory ---------------------------------------------------------------
  * Mapped, portable host memory: kernels write kNN records straight into it (pass it as the

@@ -6,17 +6,20 @@ mirror of the reference operator API (UniformGrid, Point, Polygon, QueryConfigur
 PointPointRangeQuery, PointPolygonRangeQuery, PointPointKNNQuery, PointPointJoinQuery,
 PointPolygonKNNQuery, PointPolygonJoinQuery, PointTStatsQuery, PointTAggregateQuery,
 PointPointTKNNQuery, PointPointTJoinQuery, LineString and the PointLineString{Range,KNN,Join}Query
-operators).
+operators, and the PolygonPoint / LineStringPoint {Range,KNN}Query operators over geometry windows).
 """
 from . import _lib, sharding
 from .spatialIndices import UniformGrid, generateCellIDStr, getIntCellIndices, padLeadingZeroesToInt
-from .spatialObjects import LineString, LineStringSet, ObjIdDict, Point, PointWindow, Polygon, PolygonSet
+from .spatialObjects import (GeometryWindow, LineString, LineStringSet, LineStringWindow, ObjIdDict, Point, PointWindow,
+                             Polygon, PolygonSet, PolygonWindow)
 from .spatialOperators import (KNNResult, PinnedRecords, PointPointJoinQuery, PointPointKNNQuery, PointPointRangeQuery,
                                PointPolygonJoinQuery, PointPolygonKNNQuery, PointTStatsQuery, SubTrajectories,
                                TrajectoryGroups, TStatsResult, group_by_objid, sub_trajectories,
                                PointTAggregateQuery, TAggregateGroups, TAggregateResult, tagg_rows,
                                PointPointTKNNQuery, TKNNResult, PointPointTJoinQuery, TJoinResult,
                                PointPolygonTRangeQuery, PointTFilterQuery, TRangePlan,
+                               GeometryIndex, LineStringPointKNNQuery, LineStringPointRangeQuery, PolygonPointKNNQuery,
+                               PolygonPointRangeQuery,
                                PointLineStringJoinQuery, PointLineStringKNNQuery, PointLineStringRangeQuery,
                                PointPolygonRangeQuery, QueryConfiguration, QueryType, RangeResult, assign_cells,
                                bucket_by_cell, knn_merge_host, synthetic_uniform,
@@ -25,6 +28,8 @@ from .spatialStreams import Deserialization
 from .windows import SlidingKNNQuery, SlidingRangeQuery, SlidingWindows
 
 __all__ = [
+    "GeometryWindow", "PolygonWindow", "LineStringWindow", "GeometryIndex", "PolygonPointRangeQuery",
+    "LineStringPointRangeQuery", "PolygonPointKNNQuery", "LineStringPointKNNQuery",
     "LineString", "LineStringSet", "PointLineStringRangeQuery", "PointLineStringKNNQuery", "PointLineStringJoinQuery",
     "PointPointTJoinQuery", "TJoinResult",
     "PointPolygonTRangeQuery", "PointTFilterQuery", "TRangePlan",

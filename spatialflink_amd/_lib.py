@@ -43,7 +43,9 @@ FLAG_GEOJSON_CHECK = 32
 FLAG_JOIN_STREAM = 8
 (K_KNN_SCAN, K_KNN_SAMPLE, K_KNN_SELECT, K_RANGE_SCAN, K_ASSIGN, K_JOIN_PROBE, K_RANGE_TEST, K_JOIN_BUCKET,
  K_KNN_MERGE, K_CSV_PARSE, K_BUCKET, K_JOIN_COMPACT, K_TRAJ_GROUP, K_TSTATS, K_TRAJ_SELECT, K_TAGG, K_TKNN,
- K_TJOIN, K_TRANGE) = range(19)
+ K_TJOIN, K_TRANGE, K_GEOM) = range(20)
+GEOM_POLYGON = 1     # gf_geoms.kind
+GEOM_LINESTRING = 2
 
 # Every symbol include/geoflink_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = [
@@ -81,6 +83,9 @@ EXPORTS = [
     "gf_tjoin_set_table_slots",
     "gf_trange_plan_create", "gf_trange_plan_destroy", "gf_trange_plan_stats", "gf_trange_plan_set_thresholds",
     "gf_trange_points", "gf_trange_run", "gf_trange_info", "gf_tfilter_run",
+    "gf_geom_prepare", "gf_geom_index_destroy", "gf_geom_index_info", "gf_geom_index_read",
+    "gf_geom_index_set_thresholds", "gf_geom_query_create", "gf_geom_query_destroy", "gf_geom_range_run",
+    "gf_geom_knn_enqueue", "gf_geom_info",
 ]
 
 
@@ -101,6 +106,12 @@ class GfPolygons(C.Structure):
 
 class GfLineStrings(C.Structure):
     _fields_ = [("nline", C.c_int32), ("vert_off", C.c_void_p), ("vx", C.c_void_p), ("vy", C.c_void_p)]
+
+
+class GfGeoms(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("nrings", C.c_int32), ("nobj", C.c_int64), ("ring_off", C.c_void_p),
+                ("vert_off", C.c_void_p), ("vx", C.c_void_p), ("vy", C.c_void_p), ("objID", C.c_void_p),
+                ("ts", C.c_void_p)]
 
 
 class GfKnnHeader(C.Structure):
@@ -300,6 +311,16 @@ def lib():
             "gf_trange_run": ([P, P, C.POINTER(GfPoints), P, P, i64, P, P, P, P, i64, pi64, pi64], C.c_int),
             "gf_trange_info": ([P, pi64, pi64, pi64, pi64], C.c_int),
             "gf_tfilter_run": ([P, C.POINTER(GfPoints), P, i64, P, P, i64, P, P, P, P, i64, pi64, pi64], C.c_int),
+            "gf_geom_prepare": ([P, C.POINTER(GfGrid), C.POINTER(GfGeoms), C.POINTER(P)], C.c_int),
+            "gf_geom_index_destroy": ([P], None),
+            "gf_geom_index_info": ([P, pi64, pi64, pi64, pi64], C.c_int),
+            "gf_geom_index_read": ([P, P, P], C.c_int),
+            "gf_geom_index_set_thresholds": ([P, i32], C.c_int),
+            "gf_geom_query_create": ([P, C.POINTER(GfGrid), P, P, i32, d, C.c_int, C.c_int, C.POINTER(P)], C.c_int),
+            "gf_geom_query_destroy": ([P], None),
+            "gf_geom_range_run": ([P, P, P, P], C.c_int),
+            "gf_geom_knn_enqueue": ([P, P, i32, P], C.c_int),
+            "gf_geom_info": ([P, pi64, pi64, pi64, pi64], C.c_int),
         }
         for name, (argt, rest) in sig.items():
             if os.environ.get("GF_LIB_PATH") and not hasattr(L, name):

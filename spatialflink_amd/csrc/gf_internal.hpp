@@ -913,6 +913,66 @@ enum TrangeStage {
 };
 hipError_t launch_trange(gf_ctx* ctx, int stage, const TrangeArgs& a);
 
+// polygon / linestring windows (k_geom.hip, geom.cpp).  The window is CSR: object -> rings -> vertices
+// (a linestring window has no ring level: ring j IS object j, ring_off == null).
+struct GeomArgs {
+  // the window (borrowed device arrays)
+  int32_t kind;               // GF_GEOM_POLYGON / GF_GEOM_LINESTRING
+  int64_t nobj, nrings;
+  const int32_t* ring_off;    // [nobj + 1]; null for linestrings
+  const int32_t* vert_off;    // [nrings + 1]
+  const double* vx;
+  const double* vy;
+  const int64_t* objID;       // kNN
+  // the index
+  int32_t wide_vertices;
+  double minX, minY, cl;      // the grid
+  double* ring_env;           // [nrings * 4] minx, maxx, miny, maxy (PolyView's order)
+  uint8_t* ring_ok;           // [nrings] closed with >= 4 vertices / a chain of >= 2
+  uint32_t* ring_wide;        // prepare: the rings whose envelope a wave takes
+  double* env;                // [nobj * 4] x1, y1, x2, y2 (env_far's order)
+  int32_t* cells;             // [nobj * 4] cx1, cy1, cx2, cy2
+  uint8_t* valid;             // [nobj]
+  int32_t* nvert;             // [nobj] vertices of all the object's rings
+  unsigned long long* ictr;   // index counters: [0] wide rings, [1] vertices, [2] invalid objects, [3] wide objects
+  // the query
+  int32_t grid_n;
+  const int32_t* satN;
+  const int32_t* satG;
+  const double* qx;
+  const double* qy;
+  int32_t nq;
+  double r;
+  int approx, metric;
+  int knn;                    // 1: every filtered object is tested (G unused), candidates instead of bits
+  // one run
+  uint64_t* bitmap;           // range: every word written by the classify
+  uint32_t* work_short;       // [nobj] objects one lane tests
+  uint32_t* work_wide;        // [nobj] objects one wave tests
+  unsigned long long* qctr;   // [0] short entries, [1] wide entries, [2] filtered, [3] all-G, [4] set bits
+  int64_t* counts;            // range, nullable: device int64[2]
+  KnnState* st;               // kNN: st->count = candidates appended
+  double* cand_d;
+  uint32_t* cand_i;
+  int64_t* cand_o;
+};
+enum GeomStage {
+  kGeomRingEnv = 0,       // prepare: ring envelopes by lanes, the wide rings listed
+  kGeomRingEnvWide = 1,   // prepare: the listed rings by waves
+  kGeomObjects = 2,       // prepare: per-object envelope, cells, validity, vertex count
+  kGeomClassify = 3,      // filter + all-G into the bitmap + the two worklists
+  kGeomExactShort = 4,    // one lane per short object
+  kGeomExactWide = 5,     // one wave per wide object
+  kGeomCount = 6,         // range: the bitmap's count and counts[2]
+};
+hipError_t launch_geom(gf_ctx* ctx, int stage, const GeomArgs& a);
+// The record (status 0) of the candidates (cd, co, ci)[0, *count) through the sorted path, any k: two
+// stable radix sorts, (objID, d, idx) -> the first of each objID -> (d, objID, idx) (knn.cpp; the
+// k > kMaxK path of gf_knn_enqueue).  m >= the candidate count sizes the passes; *count and *maybe are
+// zeroed on the device.  Enqueued, no host read.
+int knn_sorted_record(gf_ctx* ctx, const double* cd, const int64_t* co, const uint32_t* ci, unsigned long long* count,
+                      unsigned long long* maybe, int64_t m, int32_t k, double T, int64_t idx_base, void* result);
+
 hipError_t launch_knn_sample(gf_ctx* ctx, const KnnSampleArgs& a);
 hipError_t launch_knn_scan(gf_ctx* ctx, const KnnScanArgs& a, int blocks, int unroll, int nt);
 hipError_t launch_knn_select(gf_ctx* ctx, const KnnSelectArgs& a);

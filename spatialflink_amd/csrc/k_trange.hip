@@ -45,37 +45,6 @@ static __device__ __forceinline__ bool contains_lane(double px, double py, const
   return true;
 }
 
-// one edge (p2 -> p1) of locate_in_ring's loop: true = p is on it; else `crossings` counts it
-static __device__ __forceinline__ bool ring_edge(double px, double py, double p1x, double p1y, double p2x, double p2y,
-                                                 int& crossings) {
-  if (p1x < px && p2x < px) return false;
-  if (px == p2x && py == p2y) return true;
-  if (p1y == py && p2y == py) {
-    double mn = p1x, mx = p2x;
-    if (mn > mx) { mn = p2x; mx = p1x; }
-    return px >= mn && px <= mx;
-  }
-  if (((p1y > py) && (p2y <= py)) || ((p2y > py) && (p1y <= py))) {
-    const double x1 = p1x - px, y1 = p1y - py, x2 = p2x - px, y2 = p2y - py;
-    int sgn = sign_det2x2(x1, y1, x2, y2);
-    if (sgn == 0) return true;
-    if (y2 < y1) sgn = -sgn;
-    if (sgn > 0) ++crossings;
-  }
-  return false;
-}
-
-// locate_in_ring by one whole wave (every lane calls it with the same arguments)
-static __device__ __forceinline__ int locate_in_ring_wave(double px, double py, const double* vx, const double* vy, int nv,
-                                                          const double* env, int lane) {
-  if (px > env[1] || px < env[0] || py > env[3] || py < env[2]) return kLocExterior;
-  int crossings = 0;
-  bool on = false;
-  for (int i = 1 + lane; i < nv; i += 64) on |= ring_edge(px, py, vx[i], vy[i], vx[i - 1], vy[i - 1], crossings);
-  if (__ballot(on)) return kLocBoundary;
-  return (__popcll(__ballot(crossings & 1)) & 1) ? kLocInterior : kLocExterior;
-}
-
 static __device__ __forceinline__ bool contains_wave(double px, double py, const PolyView& a, int p, int lane) {
   const int r0 = a.ring_off[p], r1 = a.ring_off[p + 1];
   const double* e = a.ring_env + 4 * r0;

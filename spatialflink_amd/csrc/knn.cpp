@@ -373,13 +373,20 @@ static int knn_scan_select(gf_knn_plan* P, int j, const gf_points* pts, int64_t 
 // by the window (an upper bound of the candidate count) and every kernel reads the counts on
 // the device: no host read, so windows queue back to back like the pipelined paths'.
 static int knn_large(gf_knn_plan* P, const gf_points* pts, void* result) {
-  gf_ctx* ctx = P->ctx;
   int st;
   const int64_t n = pts->n;
   if (P->cap < n && (st = knn_alloc_candidates(P, n))) return st;
   if ((st = launch_scan(P, 0, pts, 0, n, 0))) return st;  // T = r
   const gf_knn_plan::Lane& L = P->lane[0];
-  const int64_t mm = std::max<int64_t>(n, 1);
+  return knn_sorted_record(P->ctx, L.cand_d, L.cand_o, L.cand_i, &L.st->count, &L.st->maybe, n, P->k, P->r, P->idx_base,
+                           result);
+}
+
+int gf::knn_sorted_record(gf_ctx* ctx, const double* cd, const int64_t* co, const uint32_t* ci, unsigned long long* count,
+                          unsigned long long* maybe, int64_t m_items, int32_t k, double T, int64_t idx_base,
+                          void* result) {
+  int st;
+  const int64_t mm = std::max<int64_t>(m_items, 1);
   const int nb = radix_blocks(ctx, mm);
   const int64_t mat = (int64_t)256 * nb;  // 8-bit digits
   Arena ar;
@@ -389,9 +396,9 @@ static int knn_large(gf_knn_plan* P, const gf_points* pts, void* result) {
   ar.take(cnt, 2); ar.take(m, mat); ar.take(ms, mat + 1);
   if ((st = ar.alloc(ctx))) return st;
   KnnLargeArgs a{};
-  a.cd = L.cand_d; a.co = L.cand_o; a.ci = L.cand_i; a.k = P->k; a.T = P->r; a.idx_base = P->idx_base;
+  a.cd = cd; a.co = co; a.ci = ci; a.k = k; a.T = T; a.idx_base = idx_base;
   a.result = result; a.m = mm; a.cnt = cnt;
-  a.lane_count = &L.st->count; a.lane_maybe = &L.st->maybe;
+  a.lane_count = count; a.lane_maybe = maybe;
   GF_HIP_CHECK(ctx, launch_knn_large(ctx, 5, a));                 // counts
   int cur = 0;  // the permutation lives in perm[cur]
   // stable sort of the first cnt[pass] entries of the permutation by key fields (least

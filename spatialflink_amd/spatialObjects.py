@@ -333,3 +333,109 @@ class PointWindow:
         i = int(i)
         return Point(self.objid_strings([int(self.objID[i])])[0], float(self.x[i]), float(self.y[i]),
                      int(self.timeStampMillisec[i]), uGrid)
+
+
+def validate_geom_offsets(kind: int, nobj: int, ring_off, vert_off, nvert: int):
+    """Host-side check of a geometry window's CSR before upload (the library trusts the offsets as it
+    trusts gf_points.n): int32 range, first entry 0, non-decreasing, and each level ending where the
+    next begins.  Raises ValueError."""
+    if kind not in (_lib.GEOM_POLYGON, _lib.GEOM_LINESTRING):
+        raise ValueError("geometry window: kind must be GEOM_POLYGON or GEOM_LINESTRING")
+    if nobj < 0 or nvert < 0 or nvert > np.iinfo(np.int32).max:
+        raise ValueError("geometry window: negative or oversized counts")
+    levels = [("vert_off", np.asarray(vert_off, np.int64), nvert)]
+    if kind == _lib.GEOM_POLYGON:
+        if ring_off is None:
+            raise ValueError("geometry window: a polygon window needs ring_off")
+        levels.insert(0, ("ring_off", np.asarray(ring_off, np.int64), len(levels[0][1]) - 1))
+        if len(levels[0][1]) != nobj + 1:
+            raise ValueError("geometry window: ring_off must have nobj + 1 entries")
+    else:
+        if ring_off is not None:
+            raise ValueError("geometry window: a linestring window has no ring_off")
+        if len(levels[0][1]) != nobj + 1:
+            raise ValueError("geometry window: vert_off must have nobj + 1 entries")
+    for name, off, end in levels:
+        if off.ndim != 1 or len(off) < 1 or off[0] != 0:
+            raise ValueError(f"geometry window: {name} must start at 0")
+        if np.any(np.diff(off) < 0):
+            raise ValueError(f"geometry window: {name} must be non-decreasing")
+        if off[-1] != end:
+            raise ValueError(f"geometry window: {name} must end at {end}, not {int(off[-1])}")
+
+
+@dataclass
+class GeometryWindow:
+    """One window of polygons or linestrings as device CSR (torch CUDA tensors): the window side of
+    PolygonPoint* / LineStringPoint* queries (Deserialization.PolygonStream / LineStringStream).
+    Polygons: object i owns rings [ring_off[i], ring_off[i+1]), ring j vertices [vert_off[j],
+    vert_off[j+1]); linestrings: no ring_off, object i owns vertices [vert_off[i], vert_off[i+1]).
+    Rings are taken as given (not closed for the caller): an unclosed or too short ring makes its
+    object invalid, and an invalid object is never selected."""
+
+    kind: int
+    ring_off: "object"
+    vert_off: "object"
+    vx: "object"
+    vy: "object"
+    objID: "object"
+    timeStampMillisec: "object"
+    nobj: int
+    start: int = 0
+    end: int = 0
+
+    @property
+    def n(self) -> int:
+        return int(self.nobj)
+
+    @classmethod
+    def from_csr(cls, kind, ring_off, vert_off, vx, vy, objID=None, ts=None, device=None, start=0, end=0):
+        import torch
+
+        vx = np.ascontiguousarray(vx, np.float64)
+        vy = np.ascontiguousarray(vy, np.float64)
+        if vx.shape != vy.shape or vx.ndim != 1:
+            raise ValueError("geometry window: vx and vy must be equal-length vectors")
+        nobj = (len(ring_off) if kind == _lib.GEOM_POLYGON and ring_off is not None else len(vert_off)) - 1
+        validate_geom_offsets(kind, nobj, ring_off, vert_off, len(vx))
+        objID = np.arange(nobj, dtype=np.int64) if objID is None else np.asarray(objID, np.int64)
+        ts = np.zeros(nobj, dtype=np.int64) if ts is None else np.asarray(ts, np.int64)
+        if len(objID) != nobj or len(ts) != nobj:
+            raise ValueError("geometry window: objID and ts must have one entry per object")
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt)).to(dev)  # noqa: E731
+        ro = t(ring_off, np.int32) if kind == _lib.GEOM_POLYGON else None
+        return cls(int(kind), ro, t(vert_off, np.int32), t(vx, np.float64), t(vy, np.float64), t(objID, np.int64),
+                   t(ts, np.int64), int(nobj), start, end)
+
+    def c_struct(self) -> _lib.GfGeoms:
+        p = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        nrings = int(self.vert_off.numel()) - 1 if self.kind == _lib.GEOM_POLYGON else 0  # validated: ring_off ends there
+        return _lib.GfGeoms(self.kind, nrings, self.nobj, p(self.ring_off), p(self.vert_off), p(self.vx), p(self.vy),
+                            p(self.objID), p(self.timeStampMillisec))
+
+
+class PolygonWindow(GeometryWindow):
+    @classmethod
+    def from_polygons(cls, polygons, objID=None, ts=None, device=None, start=0, end=0):
+        """polygons: a list of ring lists, each ring a list of (x, y); ring 0 is the shell."""
+        ring_off, vert_off, vx, vy = [0], [0], [], []
+        for rings in polygons:
+            for ring in rings:
+                vx += [float(v[0]) for v in ring]
+                vy += [float(v[1]) for v in ring]
+                vert_off.append(len(vx))
+            ring_off.append(len(vert_off) - 1)
+        return cls.from_csr(_lib.GEOM_POLYGON, ring_off, vert_off, vx, vy, objID, ts, device, start, end)
+
+
+class LineStringWindow(GeometryWindow):
+    @classmethod
+    def from_lines(cls, lines, objID=None, ts=None, device=None, start=0, end=0):
+        """lines: a list of open chains, each a list of (x, y)."""
+        vert_off, vx, vy = [0], [], []
+        for line in lines:
+            vx += [float(v[0]) for v in line]
+            vy += [float(v[1]) for v in line]
+            vert_off.append(len(vx))
+        return cls.from_csr(_lib.GEOM_LINESTRING, None, vert_off, vx, vy, objID, ts, device, start, end)

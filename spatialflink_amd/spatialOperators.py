@@ -27,7 +27,8 @@ import numpy as np
 
 from . import _lib
 from .spatialIndices import UniformGrid, generateCellIDStr
-from .spatialObjects import LineString, LineStringSet, Point, PointWindow, Polygon, PolygonSet
+from .spatialObjects import (GeometryWindow, LineString, LineStringSet, LineStringWindow, Point, PointWindow, Polygon,
+                             PolygonSet, PolygonWindow)
 
 
 class QueryType(Enum):
@@ -1528,7 +1529,167 @@ class PointPointTJoinQuery:
                 g.close()
 
 
+# ----------------------------------------------------------------------------------------
+# polygon / linestring windows against query points
+# ----------------------------------------------------------------------------------------
+class GeometryIndex:
+    """gf_geom_prepare of one GeometryWindow on one grid: per-object envelopes, cell rectangles,
+    validity and vertex counts, reusable by many queries (the window's tensors are borrowed and kept
+    alive here)."""
+
+    def __init__(self, window: GeometryWindow, grid: UniformGrid):
+        self.ctx = _lib.context(window.vert_off.device.index)
+        self.handle = C.c_void_p()
+        self.prepare(window, grid)
+
+    def prepare(self, window: GeometryWindow, grid: UniformGrid = None):
+        """Async: this index for `window` (the next window of a continuous query): the threshold stays, the
+        device arrays are reused and only grow, so a window no larger than an earlier one allocates nothing
+        and does not wait."""
+        grid = grid or self.grid
+        g = window.c_struct()
+        _lib.check(_lib.lib().gf_geom_prepare(self.ctx.handle, C.byref(grid.c_grid), C.byref(g), C.byref(self.handle)),
+                   self.ctx.handle, "gf_geom_prepare")
+        self.window, self.grid = window, grid
+
+    def info(self) -> dict:
+        v = [C.c_int64() for _ in range(4)]
+        _lib.check(_lib.lib().gf_geom_index_info(self.handle, *(C.byref(c) for c in v)), self.ctx.handle, "gf_geom_index_info")
+        return dict(zip(("nobj", "nvert", "invalid", "wide"), (c.value for c in v)))
+
+    def read(self):
+        """(env [nobj, 4] = x1, y1, x2, y2; cells [nobj, 4] = cx1, cy1, cx2, cy2) as numpy arrays"""
+        n = self.window.nobj
+        env, cells = np.zeros((n, 4), np.float64), np.zeros((n, 4), np.int32)
+        _lib.check(_lib.lib().gf_geom_index_read(self.handle, env.ctypes.data, cells.ctypes.data), self.ctx.handle,
+                   "gf_geom_index_read")
+        return env, cells
+
+    def set_thresholds(self, wide_vertices: int = 0):
+        _lib.check(_lib.lib().gf_geom_index_set_thresholds(self.handle, int(wide_vertices)), self.ctx.handle,
+                   "gf_geom_index_set_thresholds")
+
+    def close(self):
+        h = getattr(self, "handle", None)
+        if h and _lib._lib is not None:
+            _lib._lib.gf_geom_index_destroy(h)
+        self.handle = None
+
+    def __del__(self):
+        self.close()
+
+
+class _GeomWindowQuery(SpatialOperator):
+    """What the four geometry-window operators share: the cached gf_geom_query of a point set and the
+    index of the window (prepared here unless the caller shares one)."""
+
+    _destroy_name = "gf_geom_query_destroy"
+    _kind = _lib.GEOM_POLYGON
+
+    def query(self, device: int, queryPoints, queryRadius: float):
+        """(context, gf_geom_query) of this point set on `device` (cached by query contents)."""
+        _require_supported(self.conf)
+        qs = list(queryPoints)
+        qx = np.array([q.x for q in qs], np.float64)
+        qy = np.array([q.y for q in qs], np.float64)
+        ctx = _lib.context(device)
+        key = (ctx.device, tuple(qx.tolist()), tuple(qy.tolist()), float(queryRadius),
+               bool(self.conf.approximateQuery), int(self.conf.distanceMetric))
+        q = self._plans.get(key)
+        if q is None:
+            q = C.c_void_p()
+            st = _lib.lib().gf_geom_query_create(ctx.handle, C.byref(self.index.c_grid), qx.ctypes.data, qy.ctypes.data,
+                                                 len(qs), float(queryRadius), int(self.conf.approximateQuery),
+                                                 int(self.conf.distanceMetric), C.byref(q))
+            _lib.check(st, ctx.handle, "gf_geom_query_create")
+            self._plans.put(key, q)
+        self._last = (ctx, q)
+        return ctx, q
+
+    def _index(self, window: GeometryWindow, index):
+        if window.kind != self._kind:
+            raise ValueError(f"{type(self).__name__}: the window holds the other kind of geometry")
+        if index is None:
+            return GeometryIndex(window, self.index)
+        if index.window is not window:
+            raise ValueError("the index was prepared for another window")
+        return index
+
+    def info(self) -> dict:
+        """gf_geom_info of the last run: filtered, all_guaranteed, tested, wave_path"""
+        ctx, q = self._last
+        v = [C.c_int64() for _ in range(4)]
+        _lib.check(_lib.lib().gf_geom_info(q, *(C.byref(c) for c in v)), ctx.handle, "gf_geom_info")
+        return dict(zip(("filtered", "all_guaranteed", "tested", "wave_path"), (c.value for c in v)))
+
+    def __del__(self):
+        plans = getattr(self, "_plans", None)
+        if plans is not None:
+            plans.close()
+
+
+class PolygonPointRangeQuery(_GeomWindowQuery):
+    """range/PolygonPointRangeQuery.java -- a window of polygons against a set of query points."""
+
+    def run(self, window: GeometryWindow, queryPointSet, queryRadius: float, index: GeometryIndex = None) -> RangeResult:
+        import torch
+
+        ix = self._index(window, index)
+        ctx, q = self.query(window.vert_off.device.index, queryPointSet, queryRadius)
+        dev = window.vert_off.device
+        bitmap = torch.zeros(max(1, (window.nobj + 63) // 64), dtype=torch.int64, device=dev)
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().gf_geom_range_run(q, ix.handle, bitmap.data_ptr(), counts.data_ptr()), ctx.handle,
+                   "gf_geom_range_run")
+        res = RangeResult(window, bitmap, counts, None, 1, ctx)
+        if index is None:
+            ctx.synchronize()  # the index made here goes with this call
+            ix.close()
+        return res
+
+
+class LineStringPointRangeQuery(PolygonPointRangeQuery):
+    """range/LineStringPointRangeQuery.java -- a window of linestrings against a set of query points."""
+
+    _kind = _lib.GEOM_LINESTRING
+
+
+class PolygonPointKNNQuery(_GeomWindowQuery):
+    """knn/PolygonPointKNNQuery.java -- the k polygons of a window nearest to one query point within r."""
+
+    def enqueue(self, window: GeometryWindow, queryPoint: Point, queryRadius: float, k: int, record, index: GeometryIndex):
+        """Async: the window's record into `record` (a torch uint8 device tensor of knn_record_bytes(k) or
+        an address); `index` must outlive the record's completion."""
+        ix = self._index(window, index)
+        ctx, q = self.query(window.vert_off.device.index, [queryPoint], queryRadius)
+        addr = record if isinstance(record, int) else record.data_ptr()
+        _lib.check(_lib.lib().gf_geom_knn_enqueue(q, ix.handle, int(k), C.c_void_p(addr)), ctx.handle, "gf_geom_knn_enqueue")
+        return ctx
+
+    def run(self, window: GeometryWindow, queryPoint: Point, queryRadius: float, k: int, index: GeometryIndex = None) -> KNNResult:
+        import torch
+
+        if k is None or int(k) < 1:
+            raise ValueError("k must be >= 1 (PriorityQueue initialCapacity < 1)")
+        ix = self._index(window, index)
+        rec = torch.zeros(knn_record_bytes(k), dtype=torch.uint8, device=window.vert_off.device)
+        self.enqueue(window, queryPoint, queryRadius, k, rec, ix)
+        raw = rec.cpu().numpy().tobytes()  # (waits for the stream)
+        if index is None:
+            ix.close()
+        st, o, d, i = decode_knn_record(raw, int(k))
+        assert st == 0, "a geometry-window record is always final"
+        return KNNResult(window.start, window.end, o, d, i)
+
+
+class LineStringPointKNNQuery(PolygonPointKNNQuery):
+    """knn/LineStringPointKNNQuery.java -- the k linestrings of a window nearest to one query point within r."""
+
+    _kind = _lib.GEOM_LINESTRING
+
+
 __all__ = [
+    "GeometryIndex", "PolygonPointRangeQuery", "LineStringPointRangeQuery", "PolygonPointKNNQuery", "LineStringPointKNNQuery",
     "LineString", "LineStringSet", "PointLineStringRangeQuery", "PointLineStringKNNQuery", "PointLineStringJoinQuery",
     "PointPointTJoinQuery", "TJoinResult",
     "PointPolygonTRangeQuery", "PointTFilterQuery", "TRangePlan",
