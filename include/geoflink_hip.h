@@ -1015,6 +1015,7 @@ int  gf_tfilter_run(gf_traj_groups* g, const gf_points* pts, const int64_t* id_s
  *     reference leaves a null JTS object and throws later.  Non-finite vertex coordinates are outside
  *     this contract.  The offset arrays are trusted to be monotone and in bounds, as gf_points.n is.
  * Not covered: RealTime mode, Flink's triggers and sliding assignment, sharding across GPUs, JNI.
+ * (Polygon and linestring QUERIES against these windows: the next block.)
  *
  * gf_geoms: polygons -- object i owns rings [ring_off[i], ring_off[i+1]); ring j owns vertices
  * [vert_off[j], vert_off[j+1]).  Linestrings -- ring_off == NULL, object i owns vertices
@@ -1073,6 +1074,86 @@ int  gf_geom_range_run(gf_geom_query* q, gf_geom_index* ix, uint64_t* bitmap, in
 int  gf_geom_knn_enqueue(gf_geom_query* q, gf_geom_index* ix, int32_t k, void* result);
 int  gf_geom_info(const gf_geom_query* q, int64_t* filtered, int64_t* all_guaranteed, int64_t* tested,
                   int64_t* wave_path);
+
+/* ---- geometry windows against polygon and linestring queries: range and kNN --------------------
+ * range/PolygonPolygonRangeQuery.java:110-193, PolygonLineStringRangeQuery.java:111-197,
+ * LineStringPolygonRangeQuery.java, LineStringLineStringRangeQuery.java:148-193 and
+ * knn/PolygonPolygonKNNQuery.java:139-213, PolygonLineStringKNNQuery.java, LineStringPolygonKNNQuery.java,
+ * LineStringLineStringKNNQuery.java (WindowBased): the WINDOW holds geometries (block above, rules 1 and
+ * 6), the query is a set of polygons or of linestrings.  Four pairs of kinds, one gf_geom_query: it runs
+ * through gf_geom_range_run, gf_geom_knn_enqueue, gf_geom_info and gf_geom_query_destroy against an index
+ * of either window kind.  The contract (derived from the reference and JTS 1.16.1, nothing was run on a JVM):
+ *  1. Query geometries.  nq >= 1 geometries of ONE kind (kNN: exactly one), host CSR (gf_polygons /
+ *     gf_linestrings).  Each carries boundingBox and gridIDsSet exactly as a window object does: the
+ *     shell's / the chain's vertex envelope, and the unclamped cell rectangle R_q =
+ *     HelperClass.assignGridCellID(bbox).
+ *  2. Query side.  g = getGuaranteedNeighboringLayers(r), c = getCandidateNeighboringLayers(r).  The
+ *     operators' loop (PolygonPolygonRangeQuery.java:118-128; UniformGrid.java:193-222, 399-426) gives
+ *       G = the union over the queries and over every cell of R_q of getGuaranteedNeighboringCells(r, cell):
+ *           g < 0 nothing; g == 0 the cell itself with NO validKey (UniformGrid.java:171-174), so the cells
+ *           of R_q outside the grid are members; g > 0 the valid cells within g layers;
+ *       N = G u C, C = the valid cells within c layers of a cell of R_q, only when c > 0.
+ *     These are NOT the point-query rules of the block above: (a) getNeighboringCells is never called, so
+ *     there is no GF_ERR_LAYERS -- c <= 0 is an empty C; (b) r == 0 (c = 0, g = -1) gives N = {} and
+ *     selects nothing, it does not select the whole grid.  A negative or NaN r selects nothing either.
+ *     Cells are (cx, cy) pairs in or out of the grid; indices saturate like Java (int).
+ *     Deviation: g == 0 with nq > 1 and some R_q leaving the grid -- G outside the grid is then a union of
+ *     rectangles, whose cover test is not implemented -- is refused by create with GF_ERR_ARG.  With
+ *     nq == 1 the out-of-grid members of G and N are the rectangle R_q itself and are handled exactly: an
+ *     object has a cell in N iff the tables say so or its rectangle meets R_q, and all its cells in G iff
+ *     the tables say so or its rectangle lies within R_q.
+ *  3. Range.  Rule 3 of the block above, word for word, with these N and G: the filter (some rectangle
+ *     cell in N), then emitted once iff every rectangle cell is in G, or else the first query of the set,
+ *     in order, with d <= r.  Exact: d = DistanceFunctions.getDistance(query, object), rule 5, either
+ *     metric.  Approximate: d = getBBoxBBoxMinEuclideanDistance(query.boundingBox, object.boundingBox)
+ *     (DistanceFunctions.java:298-361; the query's box FIRST in all eight operators -- the kNN operators'
+ *     getPolygonPolygonBBox... / getPolygonLineStringBBox... wrappers pass (query, object) on): with the
+ *     query box (x1, y1, x2, y2) and the object box (p1, q1, p2, q2),
+ *       p2 <= x1: q2 <= y1 -> |(x1, y1) (p2, q2)|; q1 >= y2 -> |(x1, y2) (p2, q1)|; else border((p2, q1); x = x1)
+ *       p1 >= x2: q2 <= y1 -> |(x2, y1) (p1, q2)|; q1 >= y2 -> |(x2, y2) (p1, q1)|; else border((p1, q1); x = x2)
+ *       else:     q2 <= y1 -> border((p1, q2); y = y1);  q1 >= y2 -> border((p1, q1); y = y2);  else 0,
+ *     border = getPointLineStringNearestBBoxBorderMinEuclideanDistance (its x1 == x2 test first), distances
+ *     sqrt(dy*dy + dx*dx) whatever `metric` says.
+ *  4. kNN.  One query.  Candidates: the objects with a rectangle cell in N (G unused) and d <= r.  The
+ *     record: rule 4 of the block above, unchanged.
+ *  5. The exact distance: JTS Geometry.distance -> DistanceOp(query, object), terminate distance 0.
+ *     (a) Containment, both ways: for a query polygon, the object's FIRST coordinate (first shell vertex /
+ *         first chain vertex; ConnectedElementLocationFilter) located by PointLocator -- not EXTERIOR
+ *         (boundary counts as inside, inside a hole is exterior) -> d = 0; then the same with the query's
+ *         first coordinate in an object polygon.  A linestring never contains anything, closed or not.
+ *     (b) Otherwise the minimum, by `d < md`, over every (query ring or chain, object ring or chain) and
+ *         every pair of their segments of Distance.segmentToSegment(A, B, C, D), AB the query's:
+ *         A == B -> pointToSegment(A, C, D); C == D -> pointToSegment(D, A, B); the envelopes of AB and CD
+ *         disjoint -> no intersection; else denom = (B.x-A.x)(D.y-C.y) - (B.y-A.y)(D.x-C.x), denom == 0 ->
+ *         no intersection, else r = ((A.y-C.y)(D.x-C.x) - (A.x-C.x)(D.y-C.y)) / denom, s = ((A.y-C.y)(B.x-A.x)
+ *         - (A.x-C.x)(B.y-A.y)) / denom, no intersection iff r < 0 || r > 1 || s < 0 || s > 1.  No
+ *         intersection -> the minimum of pointToSegment(A, C, D), (B, C, D), (C, A, B), (D, A, B); otherwise
+ *         0.0.  pointToSegment and the point-point distance under `metric` are those of the block above.
+ *         JTS stops at md <= 0 and skips a pair of lines whose envelope distance exceeds the minimum so
+ *         far; the contract is the plain minimum (the skip can change JTS's own result only
+ *         through rounding, by a few ulp, in one branch).
+ *     (c) Assumption: every hole of a polygon, query or object, lies inside its shell's envelope, as in a
+ *         valid JTS polygon (rule 1 of the block above).  A query is not walked for an object whose
+ *         boundingBox -- the SHELL's envelope -- is provably farther than r from the query's; a polygon with
+ *         a hole outside its shell's envelope may therefore be reported farther than the plain minimum.
+ *  6. Errors, before any device call: rule 5 of the block above, and a query set with nq < 1, a null
+ *     array, offsets not starting at 0, a polygon without a ring, a ring of fewer than 4 vertices or
+ *     unclosed, or a chain of fewer than 2 vertices: GF_ERR_ARG from create.  The refusal of rule 2.
+ *     Invalid WINDOW objects: rule 6 of the block above.
+ * Not covered: RealTime mode, the geometry-stream joins, sliding panes, sharding, JNI.
+ *
+ * gf_geom_query_create_polygons / _linestrings (once per continuous query): the N / G tables of the
+ * rectangles, the query CSR, per ring its envelope and the envelopes of its runs of 32 segments (as the
+ * linestring plans cut theirs), per query its boundingBox and rectangle.
+ * gf_geom_query_set_chain_mode (tests, tools): 0 = the run envelopes prune (default), 1 = no run envelope
+ * is consulted; results are identical.  GF_ERR_ARG for a point query.
+ * Objects of at least wide_vertices vertices are tested by one wave whose lanes stride the OBJECT's
+ * segments; results are identical for any value.  gf_geom_info reads as for a point query. */
+int  gf_geom_query_create_polygons(gf_ctx* ctx, const gf_grid* g, const gf_polygons* polys, double r, int approximate,
+                                   int metric, gf_geom_query** out);
+int  gf_geom_query_create_linestrings(gf_ctx* ctx, const gf_grid* g, const gf_linestrings* lines, double r,
+                                      int approximate, int metric, gf_geom_query** out);
+int  gf_geom_query_set_chain_mode(gf_geom_query* q, int mode);
 
 /* ---- pinned host memory ---------------------------------------------------------------
  * Mapped, portable host memory: kernels write kNN records straight into it (pass it as the

@@ -6,7 +6,8 @@ mirror of the reference operator API (UniformGrid, Point, Polygon, QueryConfigur
 PointPointRangeQuery, PointPolygonRangeQuery, PointPointKNNQuery, PointPointJoinQuery,
 PointPolygonKNNQuery, PointPolygonJoinQuery, PointTStatsQuery, PointTAggregateQuery,
 PointPointTKNNQuery, PointPointTJoinQuery, LineString and the PointLineString{Range,KNN,Join}Query
-operators, and the PolygonPoint / LineStringPoint {Range,KNN}Query operators over geometry windows).
+operators, the PolygonPoint / LineStringPoint {Range,KNN}Query operators over geometry windows, and the
+{Polygon,LineString}{Polygon,LineString}{Range,KNN}Query operators: geometry windows against geometry queries).
 """
 from . import _lib, sharding
 from .spatialIndices import UniformGrid, generateCellIDStr, getIntCellIndices, padLeadingZeroesToInt
@@ -20,6 +21,9 @@ from .spatialOperators import (KNNResult, PinnedRecords, PointPointJoinQuery, Po
                                PointPolygonTRangeQuery, PointTFilterQuery, TRangePlan,
                                GeometryIndex, LineStringPointKNNQuery, LineStringPointRangeQuery, PolygonPointKNNQuery,
                                PolygonPointRangeQuery,
+                               PolygonPolygonRangeQuery, PolygonLineStringRangeQuery, LineStringPolygonRangeQuery,
+                               LineStringLineStringRangeQuery, PolygonPolygonKNNQuery, PolygonLineStringKNNQuery,
+                               LineStringPolygonKNNQuery, LineStringLineStringKNNQuery,
                                PointLineStringJoinQuery, PointLineStringKNNQuery, PointLineStringRangeQuery,
                                PointPolygonRangeQuery, QueryConfiguration, QueryType, RangeResult, assign_cells,
                                bucket_by_cell, knn_merge_host, synthetic_uniform,
@@ -28,6 +32,8 @@ from .spatialStreams import Deserialization
 from .windows import SlidingKNNQuery, SlidingRangeQuery, SlidingWindows
 
 __all__ = [
+    "PolygonPolygonRangeQuery", "PolygonLineStringRangeQuery", "LineStringPolygonRangeQuery", "LineStringLineStringRangeQuery",
+    "PolygonPolygonKNNQuery", "PolygonLineStringKNNQuery", "LineStringPolygonKNNQuery", "LineStringLineStringKNNQuery",
     "GeometryWindow", "PolygonWindow", "LineStringWindow", "GeometryIndex", "PolygonPointRangeQuery",
     "LineStringPointRangeQuery", "PolygonPointKNNQuery", "LineStringPointKNNQuery",
     "LineString", "LineStringSet", "PointLineStringRangeQuery", "PointLineStringKNNQuery", "PointLineStringJoinQuery",

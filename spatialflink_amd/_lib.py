@@ -86,6 +86,7 @@ EXPORTS = [
     "gf_geom_prepare", "gf_geom_index_destroy", "gf_geom_index_info", "gf_geom_index_read",
     "gf_geom_index_set_thresholds", "gf_geom_query_create", "gf_geom_query_destroy", "gf_geom_range_run",
     "gf_geom_knn_enqueue", "gf_geom_info",
+    "gf_geom_query_create_polygons", "gf_geom_query_create_linestrings", "gf_geom_query_set_chain_mode",
 ]
 
 
@@ -321,6 +322,11 @@ def lib():
             "gf_geom_range_run": ([P, P, P, P], C.c_int),
             "gf_geom_knn_enqueue": ([P, P, i32, P], C.c_int),
             "gf_geom_info": ([P, pi64, pi64, pi64, pi64], C.c_int),
+            "gf_geom_query_create_polygons": ([P, C.POINTER(GfGrid), C.POINTER(GfPolygons), d, C.c_int, C.c_int,
+                                              C.POINTER(P)], C.c_int),
+            "gf_geom_query_create_linestrings": ([P, C.POINTER(GfGrid), C.POINTER(GfLineStrings), d, C.c_int, C.c_int,
+                                                 C.POINTER(P)], C.c_int),
+            "gf_geom_query_set_chain_mode": ([P, C.c_int], C.c_int),
         }
         for name, (argt, rest) in sig.items():
             if os.environ.get("GF_LIB_PATH") and not hasattr(L, name):

@@ -1,6 +1,8 @@
 // geom.cpp -- polygon / linestring windows against query points: the index of one window
 // (gf_geom_prepare; prepared again for the next window, its arrays reused), the query built once per continuous query (its pure host part is
-// gf_geom_plan.hpp's), gf_geom_range_run and gf_geom_knn_enqueue.  The kernels are in k_geom.hip; the
+// gf_geom_plan.hpp's), gf_geom_range_run and gf_geom_knn_enqueue.  A query is a point set or, through
+// gf_geom_query_create_polygons / _linestrings, a set of polygons or linestrings; the same run calls take
+// either.  The kernels are in k_geom.hip (point queries) and k_geompair.hip (geometry queries); the
 // kNN record comes from the library's own selection (launch_knn_select for k <= kMaxK, the sorted path
 // knn_sorted_record above it).  Everything is enqueued on the context stream; only the calls marked
 // sync in the header wait.  The objects' device arrays are gf_group.hpp's typed holders (grow-only).
@@ -11,6 +13,7 @@
 
 #include <cstring>
 
+#include "gf_chain_plan.hpp"
 #include "gf_geom_plan.hpp"
 #include "gf_group.hpp"
 
@@ -43,6 +46,13 @@ struct gf_geom_query {
   GeomTables tab;  // host copy: the sets' sizes
   DevArr<int32_t> satN, satG;
   DevArr<double> qx, qy;
+  // a polygon / linestring query set (qkind != 0; the kernels of k_geompair.hip): CSR, envelopes, runs
+  int32_t qkind = 0;
+  int plain = 0;        // gf_geom_query_set_chain_mode: 1 = no run envelope is consulted
+  int32_t corner = 0;   // guaranteed layers 0, one query, its rectangle leaves the grid
+  int32_t q_rect[4] = {0, 0, 0, 0};
+  DevArr<int32_t> q_ring_off, q_vert_off, q_run_off;
+  DevArr<double> qvx, qvy, q_ring_env, q_env, q_run_env;
   DevArr<unsigned long long> ctr;  // of the last run
   // kNN candidates (grow-only, sized by the largest window so far)
   DevArr<KnnState> st;
@@ -206,6 +216,98 @@ extern "C" int gf_geom_query_create(gf_ctx* ctx, const gf_grid* g, const double*
   return GF_OK;
 }
 
+// A query set of polygons (ring_off != null) or linestrings: every ring / chain goes through
+// gf_chain_plan.hpp as one line -- its envelope and its runs of kChainRun segments.
+static int geom_query_create_set(gf_ctx* ctx, const gf_grid* g, int32_t qkind, int32_t nq, const int32_t* ring_off,
+                                 const int32_t* vert_off, const double* vx, const double* vy, double r, int approximate,
+                                 int metric, gf_geom_query** out, const char* who) {
+  if (!out || !grid_ok(g) || (metric != 0 && metric != 1) || g->n > kGeomMaxGrid ||
+      !geom_query_set_valid(nq, ring_off, vert_off, vx, vy))
+    return set_err(ctx, GF_ERR_ARG, std::string(who) + ": bad argument (a grid, a metric, >= 1 legal geometries)");
+  *out = nullptr;
+  if (!ctx) return GF_ERR_ARG;
+  // no getNeighboringCells here: candidate layers <= 0 is an empty N, not an error
+  const int32_t gl = guaranteed_layers(g->cellLength, r), cl = candidate_layers(g->cellLength, r);
+  gf_linestrings rings{ring_off ? ring_off[nq] : nq, vert_off, vx, vy};
+  ChainTables T;
+  chain_build(rings, kChainRun, T);
+  std::vector<int32_t> ro, rects(4 * (size_t)nq);
+  std::vector<double> env(4 * (size_t)nq), renv(4 * (size_t)rings.nline);
+  for (int32_t j = 0; j < rings.nline; ++j) {  // x1, y1, x2, y2 -> PolyView's minx, maxx, miny, maxy
+    const double* b = &T.bbox[4 * (size_t)j];
+    double* e = &renv[4 * (size_t)j];
+    e[0] = b[0]; e[1] = b[2]; e[2] = b[1]; e[3] = b[3];
+  }
+  for (int32_t q = 0; q < nq; ++q) {  // boundingBox: the shell's / the chain's; gridIDsSet: its cell rectangle
+    const double* b = &T.bbox[4 * (size_t)(ring_off ? ring_off[q] : q)];
+    std::memcpy(&env[4 * (size_t)q], b, 4 * sizeof(double));
+    int32_t* c = &rects[4 * (size_t)q];
+    c[0] = cell_index(b[0], g->minX, g->cellLength);
+    c[1] = cell_index(b[1], g->minY, g->cellLength);
+    c[2] = cell_index(b[2], g->minX, g->cellLength);
+    c[3] = cell_index(b[3], g->minY, g->cellLength);
+  }
+  gf_geom_query* Q = new gf_geom_query();
+  bool leaves = false;
+  if (geom_build_tables_rects(g->n, nq, rects.data(), gl, cl, Q->tab, &leaves)) {
+    delete Q;
+    return set_err(ctx, GF_ERR_ARG, std::string(who) + ": grid too large for the summed-area tables");
+  }
+  if (leaves && nq > 1) {  // the deviation of contract 2: G outside the grid as a union of rectangles
+    delete Q;
+    return set_err(ctx, GF_ERR_ARG, std::string(who) + ": guaranteed layers 0 with several queries and a query rectangle "
+                                                       "that leaves the grid is not supported");
+  }
+  int st = bind(ctx);
+  if (st) { delete Q; return st; }
+  Q->ctx = ctx;
+  Q->grid = *g;
+  Q->nq = nq;
+  Q->r = r;
+  Q->approx = approximate != 0;
+  Q->metric = metric;
+  Q->qkind = qkind;
+  Q->corner = leaves;
+  std::memcpy(Q->q_rect, rects.data(), sizeof(Q->q_rect));
+  if (ring_off) ro.assign(ring_off, ring_off + nq + 1);
+  else ro.assign(1, 0);  // (never read: a linestring query has no ring level)
+  std::vector<unsigned long long> zero(kQueryCounters, 0);
+  std::vector<KnnState> st0(1);
+  std::memset(st0.data(), 0, sizeof(KnnState));
+  if ((st = upload(ctx, Q->satN, Q->tab.satN)) || (st = upload(ctx, Q->satG, Q->tab.satG)) ||
+      (st = upload(ctx, Q->q_ring_off, ro)) || (st = upload(ctx, Q->q_vert_off, T.vert_off)) || (st = upload(ctx, Q->qvx, T.vx)) ||
+      (st = upload(ctx, Q->qvy, T.vy)) || (st = upload(ctx, Q->q_ring_env, renv)) || (st = upload(ctx, Q->q_env, env)) ||
+      (st = upload(ctx, Q->q_run_off, T.run_off)) || (st = upload(ctx, Q->q_run_env, T.run_env)) ||
+      (st = upload(ctx, Q->ctr, zero)) || (st = upload(ctx, Q->st, st0))) {
+    gf_geom_query_destroy(Q);
+    return st;
+  }
+  Q->tab.satN = std::vector<int32_t>();  // the host keeps the counts only
+  Q->tab.satG = std::vector<int32_t>();
+  *out = Q;
+  return GF_OK;
+}
+
+extern "C" int gf_geom_query_create_polygons(gf_ctx* ctx, const gf_grid* g, const gf_polygons* polys, double r, int approximate,
+                                             int metric, gf_geom_query** out) {
+  if (!polys || !polys->ring_off) return set_err(ctx, GF_ERR_ARG, "gf_geom_query_create_polygons: bad argument");
+  return geom_query_create_set(ctx, g, GF_GEOM_POLYGON, polys->npoly, polys->ring_off, polys->vert_off, polys->vx, polys->vy, r,
+                               approximate, metric, out, "gf_geom_query_create_polygons");
+}
+
+extern "C" int gf_geom_query_create_linestrings(gf_ctx* ctx, const gf_grid* g, const gf_linestrings* lines, double r,
+                                                int approximate, int metric, gf_geom_query** out) {
+  if (!lines) return set_err(ctx, GF_ERR_ARG, "gf_geom_query_create_linestrings: bad argument");
+  return geom_query_create_set(ctx, g, GF_GEOM_LINESTRING, lines->nline, nullptr, lines->vert_off, lines->vx, lines->vy, r,
+                               approximate, metric, out, "gf_geom_query_create_linestrings");
+}
+
+extern "C" int gf_geom_query_set_chain_mode(gf_geom_query* Q, int mode) {
+  if (!Q || Q->qkind == 0 || (mode != 0 && mode != 1)) return GF_ERR_ARG;
+  Q->plain = mode;
+  return GF_OK;
+}
+
 // a query meets an index: same context, same grid
 static int geom_pair_ok(const gf_geom_query* Q, const gf_geom_index* X, const char* who) {
   if (!Q || !X) return GF_ERR_ARG;
@@ -227,6 +329,22 @@ static int geom_passes(gf_geom_query* Q, gf_geom_index* X, GeomArgs& a) {
   gf_ctx* ctx = Q->ctx;
   GF_HIP_CHECK(ctx, hipMemsetAsync(Q->ctr.p, 0, kQueryCounters * sizeof(unsigned long long), ctx->stream));
   if (X->geoms.nobj == 0) return GF_OK;
+  if (Q->qkind) {  // a polygon / linestring query: the same three passes with the pair distance (k_geompair.hip)
+    GeomPairArgs p{};
+    p.g = a;
+    p.qkind = Q->qkind;
+    p.q_ring_off = Q->qkind == GF_GEOM_POLYGON ? Q->q_ring_off.p : nullptr;
+    p.q_vert_off = Q->q_vert_off.p; p.qvx = Q->qvx.p; p.qvy = Q->qvy.p;
+    p.q_ring_env = Q->q_ring_env.p; p.q_env = Q->q_env.p;
+    p.q_run_off = Q->plain ? nullptr : Q->q_run_off.p;
+    p.q_run_env = Q->q_run_env.p;
+    p.corner = Q->corner;
+    std::memcpy(p.q_rect, Q->q_rect, sizeof(p.q_rect));
+    GF_HIP_CHECK(ctx, launch_geompair(ctx, kGeomPairClassify, p));
+    GF_HIP_CHECK(ctx, launch_geompair(ctx, kGeomPairShort, p));
+    if (!Q->approx) GF_HIP_CHECK(ctx, launch_geompair(ctx, kGeomPairWide, p));
+    return GF_OK;
+  }
   GF_HIP_CHECK(ctx, launch_geom(ctx, kGeomClassify, a));
   GF_HIP_CHECK(ctx, launch_geom(ctx, kGeomExactShort, a));
   if (!Q->approx) GF_HIP_CHECK(ctx, launch_geom(ctx, kGeomExactWide, a));
@@ -256,7 +374,7 @@ extern "C" int gf_geom_knn_enqueue(gf_geom_query* Q, gf_geom_index* X, int32_t k
   if (int st = geom_pair_ok(Q, X, "gf_geom_knn_enqueue")) return st;
   gf_ctx* ctx = Q->ctx;
   if (!result || k < 1 || k > kMaxKLarge || Q->nq != 1 || (X->geoms.nobj > 0 && !X->geoms.objID))
-    return set_err(ctx, GF_ERR_ARG, "gf_geom_knn_enqueue: bad argument (one query point, k >= 1, objID keys)");
+    return set_err(ctx, GF_ERR_ARG, "gf_geom_knn_enqueue: bad argument (one query point or geometry, k >= 1, objID keys)");
   int st = bind(ctx);
   if (st) return st;
   const size_t cap = (size_t)std::max<int64_t>(X->geoms.nobj, 1);

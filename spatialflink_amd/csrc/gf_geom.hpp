@@ -264,4 +264,188 @@ static __device__ __forceinline__ double chain_distance(double px, double py, co
   return md;
 }
 
+// ---- geometry-to-geometry distance (k_geompair.hip; include/geoflink_hip.h, "geometry windows against
+// polygon and linestring queries", contract 5) -------------------------------------------------------
+
+// JTS Distance.segmentToSegment(A, B, C, D) and nothing else: a degenerate segment is its point; segments
+// whose envelopes are disjoint, whose denominator is 0 (parallel or collinear) or whose parameters r, s
+// leave [0, 1] do not intersect and are at the minimum of the four point-to-segment distances (MathUtil.min,
+// `v < min` in argument order); otherwise 0.0.
+static __device__ __forceinline__ double segment_to_segment(double ax, double ay, double bx, double by, double cx, double cy,
+                                                            double dx, double dy, int metric) {
+  if (ax == bx && ay == by) return point_to_segment(ax, ay, cx, cy, dx, dy, metric);
+  if (cx == dx && cy == dy) return point_to_segment(dx, dy, ax, ay, bx, by, metric);
+  bool apart;
+  {  // Envelope.intersects(A, B, C, D)
+    const double minq = cx < dx ? cx : dx, maxq = cx > dx ? cx : dx, minp = ax < bx ? ax : bx, maxp = ax > bx ? ax : bx;
+    const double minqy = cy < dy ? cy : dy, maxqy = cy > dy ? cy : dy, minpy = ay < by ? ay : by, maxpy = ay > by ? ay : by;
+    apart = minp > maxq || maxp < minq || minpy > maxqy || maxpy < minqy;
+  }
+  if (!apart) {
+    const double denom = (bx - ax) * (dy - cy) - (by - ay) * (dx - cx);
+    if (denom == 0.0) {
+      apart = true;
+    } else {
+      const double r_num = (ay - cy) * (dx - cx) - (ax - cx) * (dy - cy);
+      const double s_num = (ay - cy) * (bx - ax) - (ax - cx) * (by - ay);
+      const double s = s_num / denom, r = r_num / denom;
+      apart = r < 0.0 || r > 1.0 || s < 0.0 || s > 1.0;
+    }
+  }
+  if (!apart) return 0.0;
+  double m = point_to_segment(ax, ay, cx, cy, dx, dy, metric);
+  const double d2 = point_to_segment(bx, by, cx, cy, dx, dy, metric);
+  if (d2 < m) m = d2;
+  const double d3 = point_to_segment(cx, cy, ax, ay, bx, by, metric);
+  if (d3 < m) m = d3;
+  const double d4 = point_to_segment(dx, dy, ax, ay, bx, by, metric);
+  if (d4 < m) m = d4;
+  return m;
+}
+
+// DistanceFunctions.getBBoxBBoxMinEuclideanDistance(bBox1, bBox2) -- DistanceFunctions.java:298-361, its
+// branches with their <= / >= as written; a, b = x1, y1, x2, y2.  The operators pass the QUERY's box first.
+static __device__ inline double bbox_bbox_distance(const double* a, const double* b) {
+  const double x1 = a[0], y1 = a[1], x2 = a[2], y2 = a[3];
+  const double p1 = b[0], q1 = b[1], p2 = b[2], q2 = b[3];
+  if (p2 <= x1) {
+    if (q2 <= y1) return pp_euclid(x1, y1, p2, q2);       // a1, b3
+    if (q1 >= y2) return pp_euclid(x1, y2, p2, q1);       // a4, b2
+    return bbox_border(p2, q1, x1, y1, x1, y2);           // b2 against a1-a4
+  } else if (p1 >= x2) {
+    if (q2 <= y1) return pp_euclid(x2, y1, p1, q2);       // a2, b4
+    if (q1 >= y2) return pp_euclid(x2, y2, p1, q1);       // a3, b1
+    return bbox_border(p1, q1, x2, y1, x2, y2);           // b1 against a2-a3
+  }
+  if (q2 <= y1) return bbox_border(p1, q2, x1, y1, x2, y1);  // b4 against a1-a2
+  if (q1 >= y2) return bbox_border(p1, q1, x2, y2, x1, y2);  // b1 against a3-a4
+  return 0.0;
+}
+
+// env_far between two boxes: true only when every point of box a is provably farther than r from every
+// point of box b.  The computed segment-to-segment distance of two segments inside the boxes is within a
+// few tens of eps x (coordinate scale) of their true distance, which is >= the true box distance; the
+// margin (1e-12 relative to the coordinates, 1e-9 relative to r) exceeds that by orders of magnitude, so a
+// pair of segments from boxes that are `far` could never have tested <= r.  An infinite or NaN bound is
+// never far.
+__device__ __forceinline__ bool box_far(double ax1, double ay1, double ax2, double ay2, double bx1, double by1, double bx2,
+                                        double by2, double r) {
+  const double dx = ax2 < bx1 ? bx1 - ax2 : (bx2 < ax1 ? ax1 - bx2 : 0.0);
+  const double dy = ay2 < by1 ? by1 - ay2 : (by2 < ay1 ? ay1 - by2 : 0.0);
+  const double scale = fabs(ax1) + fabs(ay1) + fabs(ax2) + fabs(ay2) + fabs(bx1) + fabs(by1) + fabs(bx2) + fabs(by2);
+  const double rm = r + r * 1e-9 + scale * 1e-12;
+  return dx > rm || dy > rm || dx * dx + dy * dy > rm * rm;
+}
+
+// the rings / chains [r0, r1) of ONE geometry of a CSR set (ring r0 the shell when `polygon`)
+struct GeomSide {
+  const int32_t* vert_off;
+  const double* vx;
+  const double* vy;
+  const double* ring_env;  // [rings * 4] minx, maxx, miny, maxy
+  int r0, r1;
+  bool polygon;
+};
+
+// PointLocator.locate(p, polygon) != EXTERIOR: the shell, then the holes in order (inside a hole is
+// exterior, on a hole's ring is boundary).  WAVE: by one whole wave, every lane with the same arguments.
+template <bool WAVE>
+static __device__ __forceinline__ bool side_holds(double px, double py, const GeomSide& s, int lane) {
+  for (int rg = s.r0; rg < s.r1; ++rg) {
+    const int v0 = s.vert_off[rg], nv = s.vert_off[rg + 1] - v0;
+    const int loc = WAVE ? locate_in_ring_wave(px, py, s.vx + v0, s.vy + v0, nv, s.ring_env + 4 * (size_t)rg, lane)
+                         : locate_in_ring(px, py, s.vx + v0, s.vy + v0, nv, s.ring_env + 4 * (size_t)rg);
+    if (loc == kLocBoundary) return true;
+    if (rg == s.r0) {
+      if (loc == kLocExterior) return false;
+    } else if (loc == kLocInterior) {
+      return false;
+    }
+  }
+  return true;
+}
+
+// The facet distance of query geometry q against the segments of ONE object ring / chain that this caller
+// owns: j = j0, j0 + jstep, ... < the ring's segments (the lane form owns them all: j0 = 0, jstep = 1; the
+// wave form lane l owns l, l + 64, ...).  Lowers `l`, this caller's minimum so far, with `d < l`.
+// Pruning, value-safe for every d <= r: bound = VALUE ? min(l, r) : r; an object segment whose
+// box is box_far from a query ring's envelope skips that ring, and from a run's envelope that run -- a
+// skipped pair has a computed distance > bound, so it could neither lower l nor test <= r.  q_run_off
+// null, or a ring of at most kChainPlainRunsValue runs: no run is skipped.
+template <bool VALUE>
+static __device__ __forceinline__ void pair_ring_facets(const GeomSide& q, const int32_t* q_run_off, const double* q_run_env,
+                                                        const double* ovx, const double* ovy, int onseg, int j0, int jstep,
+                                                        double r, int metric, double& l) {
+  for (int j = j0; j < onseg; j += jstep) {
+    const double cx = ovx[j], cy = ovy[j], dx = ovx[j + 1], dy = ovy[j + 1];
+    const double sx1 = cx < dx ? cx : dx, sx2 = cx < dx ? dx : cx, sy1 = cy < dy ? cy : dy, sy2 = cy < dy ? dy : cy;
+    for (int ra = q.r0; ra < q.r1; ++ra) {
+      const double* e = q.ring_env + 4 * (size_t)ra;
+      double bound = VALUE ? (l < r ? l : r) : r;
+      if (box_far(e[0], e[2], e[1], e[3], sx1, sy1, sx2, sy2, bound)) continue;
+      const int v0 = q.vert_off[ra], nseg = q.vert_off[ra + 1] - v0 - 1;
+      const double* qx = q.vx + v0;
+      const double* qy = q.vy + v0;
+      int nrun = 0, run0 = 0;
+      if (q_run_off) { run0 = q_run_off[ra]; nrun = q_run_off[ra + 1] - run0; }
+      if (nrun > kChainPlainRunsValue) {
+        for (int rn = 0; rn < nrun; ++rn) {
+          const double* re = q_run_env + 4 * (size_t)(run0 + rn);
+          bound = VALUE ? (l < r ? l : r) : r;
+          if (box_far(re[0], re[1], re[2], re[3], sx1, sy1, sx2, sy2, bound)) continue;
+          const int s0 = rn * kChainRun, s1 = s0 + kChainRun < nseg ? s0 + kChainRun : nseg;
+          for (int i = s0; i < s1; ++i) {
+            const double d = segment_to_segment(qx[i], qy[i], qx[i + 1], qy[i + 1], cx, cy, dx, dy, metric);
+            if (d < l) l = d;
+          }
+          if (l <= 0.0) return;
+        }
+      } else {
+        for (int i = 0; i < nseg; ++i) {
+          const double d = segment_to_segment(qx[i], qy[i], qx[i + 1], qy[i + 1], cx, cy, dx, dy, metric);
+          if (d < l) l = d;
+        }
+        if (l <= 0.0) return;
+      }
+    }
+    if (!VALUE && l <= r) return;  // the decision is made: some pair is within r
+  }
+}
+
+// the wave's minimum by `t < l` (a NaN never wins), the same value in every lane
+static __device__ __forceinline__ double wave_min(double l) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const double t = __shfl_xor(l, o, 64);
+    if (t < l) l = t;
+  }
+  return l;
+}
+
+// DistanceOp(query, object), terminate distance 0 (contract 5): containment both ways -- the object's first
+// coordinate in a query polygon, then the query's first coordinate in an object polygon --, then the
+// minimum over every pair of segments.  The minimum of non-NaN values by `d < md` does not depend on the
+// order, so the lane form, the wave form (the lanes stride the object's segments, the query's are
+// wave-uniform, wave_min between the object's rings) and JTS's own loop order give the same bits.
+// VALUE == false (range): the result is compared with r only and may be any pair's distance <= r.
+template <bool WAVE, bool VALUE>
+static __device__ __forceinline__ double geom_distance(const GeomSide& q, const int32_t* q_run_off, const double* q_run_env,
+                                                       const GeomSide& o, double r, int metric, int lane) {
+  {
+    const double ox = o.vx[o.vert_off[o.r0]], oy = o.vy[o.vert_off[o.r0]];
+    if (q.polygon && ox == ox && side_holds<WAVE>(ox, oy, q, lane)) return 0.0;
+    const double fx = q.vx[q.vert_off[q.r0]], fy = q.vy[q.vert_off[q.r0]];
+    if (o.polygon && fx == fx && side_holds<WAVE>(fx, fy, o, lane)) return 0.0;
+  }
+  double md = 1.7976931348623157e308;
+  for (int rb = o.r0; rb < o.r1; ++rb) {
+    const int v0 = o.vert_off[rb], onseg = o.vert_off[rb + 1] - v0 - 1;
+    double l = md;
+    pair_ring_facets<VALUE>(q, q_run_off, q_run_env, o.vx + v0, o.vy + v0, onseg, WAVE ? lane : 0, WAVE ? 64 : 1, r, metric, l);
+    md = WAVE ? wave_min(l) : l;
+    if (md <= 0.0) return md;
+    if (!VALUE && md <= r) return md;
+  }
+  return md;
+}
+
 }  // namespace gf

@@ -966,6 +966,31 @@ enum GeomStage {
   kGeomCount = 6,         // range: the bitmap's count and counts[2]
 };
 hipError_t launch_geom(gf_ctx* ctx, int stage, const GeomArgs& a);
+
+// geometry windows against polygon / linestring QUERIES (k_geompair.hip, geom.cpp): the window, the index,
+// the tables, the worklists, the bitmap and the candidates are GeomArgs' (qx, qy unused, nq = the query
+// geometries); the query set is CSR like the window (a linestring query has no ring level: ring j IS
+// query j, q_ring_off == null).
+struct GeomPairArgs {
+  GeomArgs g;
+  int32_t qkind;              // GF_GEOM_POLYGON / GF_GEOM_LINESTRING
+  const int32_t* q_ring_off;  // [nq + 1]; null for linestrings
+  const int32_t* q_vert_off;  // [q rings + 1]
+  const double* qvx;
+  const double* qvy;
+  const double* q_ring_env;   // [q rings * 4] minx, maxx, miny, maxy (PolyView's order)
+  const double* q_env;        // [nq * 4] x1, y1, x2, y2: boundingBox (the shell's / the chain's)
+  const int32_t* q_run_off;   // [q rings + 1] runs of kChainRun segments per ring; null: no run is skipped
+  const double* q_run_env;    // [runs * 4] x1, y1, x2, y2
+  int32_t corner;             // 1: guaranteed layers 0, one query, its rectangle leaves the grid
+  int32_t q_rect[4];          // that query's cell rectangle cx1, cy1, cx2, cy2
+};
+enum GeomPairStage {
+  kGeomPairClassify = 0,  // geom_classify with the out-of-grid corner of G
+  kGeomPairShort = 1,     // one lane per short object
+  kGeomPairWide = 2,      // one wave per wide object
+};
+hipError_t launch_geompair(gf_ctx* ctx, int stage, const GeomPairArgs& a);
 // The record (status 0) of the candidates (cd, co, ci)[0, *count) through the sorted path, any k: two
 // stable radix sorts, (objID, d, idx) -> the first of each objID -> (d, objID, idx) (knn.cpp; the
 // k > kMaxK path of gf_knn_enqueue).  m >= the candidate count sizes the passes; *count and *maybe are

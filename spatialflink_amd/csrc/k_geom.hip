@@ -35,28 +35,10 @@
 #define GF_TU_NAME k_geom_hip
 #include "gf_buildtag.hpp"  // first: records this unit's command-line defines
 
-#include "gf_geom.hpp"
 #include "gf_geom_plan.hpp"
+#include "gf_geom_win.hpp"  // geom_reserve, wave_sum, geom_emit: shared with k_geompair.hip
 
 namespace gf {
-
-// one slot per lane with c set: a ballot and one atomic per wave (every lane of the wave calls it)
-template <class Store>
-static __device__ __forceinline__ void geom_reserve(unsigned long long* ctr, bool c, Store&& store) {
-  const unsigned long long m = __ballot(c);
-  if (m == 0) return;
-  const int lane = threadIdx.x & 63;
-  const int leader = __ffsll((long long)m) - 1;
-  unsigned long long base = 0;
-  if (lane == leader) base = atomicAdd(ctr, (unsigned long long)__popcll(m));
-  base = __shfl(base, leader, 64);
-  if (c) store(base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull)));
-}
-
-static __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;  // lane 0 holds the sum
-}
 
 static __device__ __forceinline__ bool ring_legal(const GeomArgs& a, int32_t v0, int32_t nv) {
   if (a.kind == GF_GEOM_LINESTRING) return nv >= 2;
@@ -167,31 +149,7 @@ __global__ __launch_bounds__(kBlock) void geom_objects_kernel(GeomArgs a) {
 }
 
 __global__ __launch_bounds__(kBlock) void geom_classify_kernel(GeomArgs a) {
-  const int lane = threadIdx.x & 63;
-  unsigned long long n_filt = 0, n_allg = 0;  // this wave's (lane 0 keeps them)
-  for (int64_t i0 = (int64_t)blockIdx.x * kBlock; i0 < a.nobj; i0 += (int64_t)gridDim.x * kBlock) {  // wave-uniform
-    const int64_t i = i0 + threadIdx.x;
-    const bool in = i < a.nobj;
-    const int64_t il = in ? i : a.nobj - 1;  // clamped: the loads never branch
-    const int4 c = reinterpret_cast<const int4*>(a.cells)[il];
-    const bool ok = in && a.valid[il];
-    const int32_t nv = a.nvert[il];
-    const bool filt = ok && geom_rect_count(a.satN, a.grid_n, c.x, c.y, c.z, c.w) > 0;
-    bool allg = false;
-    if (filt && !a.knn) allg = geom_rect_count(a.satG, a.grid_n, c.x, c.y, c.z, c.w) == geom_rect_area(c.x, c.y, c.z, c.w);
-    const unsigned long long m_allg = __ballot(allg);
-    n_filt += __popcll(__ballot(filt));
-    n_allg += __popcll(m_allg);
-    if (!a.knn && lane == 0 && in) a.bitmap[i >> 6] = m_allg;
-    const bool test = filt && !allg;
-    const bool wide = test && !a.approx && nv >= a.wide_vertices;  // (the bbox distance walks nothing)
-    geom_reserve(a.qctr, test && !wide, [&](unsigned long long pos) { a.work_short[pos] = (uint32_t)i; });
-    geom_reserve(a.qctr + 1, wide, [&](unsigned long long pos) { a.work_wide[pos] = (uint32_t)i; });
-  }
-  if (lane == 0) {
-    if (n_filt) atomicAdd(a.qctr + 2, n_filt);
-    if (n_allg) atomicAdd(a.qctr + 3, n_allg);
-  }
+  geom_classify_body(a, [](const int4&) { return 0u; });  // point queries: the tables hold everything
 }
 
 static __device__ __forceinline__ PolyView poly_view(const GeomArgs& a) {
@@ -205,19 +163,6 @@ static __device__ __forceinline__ ChainView chain_view(const GeomArgs& a) {
   c.run_off = nullptr; c.vert_off = a.vert_off; c.vx = a.vx; c.vy = a.vy;  // no runs: the plain segment loop
   c.run_env = nullptr; c.metric = a.metric;
   return c;
-}
-
-// a hit of object i at distance d: its bit, or its candidate (every lane of the wave calls it)
-static __device__ __forceinline__ void geom_emit(const GeomArgs& a, bool hit, uint32_t i, double d) {
-  if (a.knn) {
-    geom_reserve(&a.st->count, hit, [&](unsigned long long pos) {
-      a.cand_d[pos] = d;  // pos < the objects tested <= the buffers' nobj entries
-      a.cand_i[pos] = i;
-      a.cand_o[pos] = a.objID[i];
-    });
-  } else if (hit) {
-    atomicOr((unsigned long long*)a.bitmap + (i >> 6), 1ull << (i & 63));
-  }
 }
 
 __global__ __launch_bounds__(kBlock) void geom_exact_short_kernel(GeomArgs a) {
@@ -249,13 +194,6 @@ __global__ __launch_bounds__(kBlock) void geom_exact_short_kernel(GeomArgs a) {
 
 // polygon_distance by one whole wave (every lane calls it with the same arguments; the same value in
 // every lane)
-static __device__ __forceinline__ double wave_min(double l) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const double t = __shfl_xor(l, o, 64);
-    if (t < l) l = t;
-  }
-  return l;
-}
 static __device__ __forceinline__ double polygon_distance_wave(double px, double py, const PolyView& a, int p, int lane) {
   const int r0 = a.ring_off[p], r1 = a.ring_off[p + 1];
   if (px == px) {  // NaN x: containment skipped, as polygon_distance

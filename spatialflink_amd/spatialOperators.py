@@ -1688,7 +1688,97 @@ class LineStringPointKNNQuery(PolygonPointKNNQuery):
     _kind = _lib.GEOM_LINESTRING
 
 
+# ----------------------------------------------------------------------------------------
+# polygon / linestring windows against polygon / linestring queries
+# ----------------------------------------------------------------------------------------
+class _GeomPairQuery(_GeomWindowQuery):
+    """The query side of the eight geometry-pair operators: a gf_geom_query built from a PolygonSet or a
+    LineStringSet (or the Polygon / LineString objects that make one), cached by the set's contents.
+    chain_mode = 1 builds the query without run-envelope pruning (tests, tools/bench_geompair.py)."""
+
+    _query_kind = _lib.GEOM_POLYGON
+    chain_mode = 0
+
+    def _query_set(self, queries):
+        if isinstance(queries, list) and len(queries) == 1 and isinstance(queries[0], (PolygonSet, LineStringSet)):
+            queries = queries[0]  # the kNN operators wrap their one query in a list
+        if self._query_kind == _lib.GEOM_POLYGON:
+            if isinstance(queries, Polygon):
+                queries = [queries]
+            return queries if isinstance(queries, PolygonSet) else PolygonSet(queries)
+        if isinstance(queries, LineString):
+            queries = [queries]
+        return queries if isinstance(queries, LineStringSet) else LineStringSet(queries)
+
+    def query(self, device: int, queries, queryRadius: float):
+        # WindowBased only: the reference's RealTime bodies of these operators differ from their window bodies
+        if self.conf.getQueryType() is not QueryType.WindowBased:
+            raise ValueError("Not yet support")
+        qset = self._query_set(queries)
+        ctx = _lib.context(device)
+        key = (ctx.device, self._query_kind, qset.digest(), float(queryRadius), bool(self.conf.approximateQuery),
+               int(self.conf.distanceMetric), int(self.chain_mode))
+        q = self._plans.get(key)
+        if q is None:
+            q = C.c_void_p()
+            polygons = self._query_kind == _lib.GEOM_POLYGON
+            name = "gf_geom_query_create_polygons" if polygons else "gf_geom_query_create_linestrings"
+            cs = qset.c_struct()
+            st = getattr(_lib.lib(), name)(ctx.handle, C.byref(self.index.c_grid), C.byref(cs), float(queryRadius),
+                                           int(self.conf.approximateQuery), int(self.conf.distanceMetric), C.byref(q))
+            _lib.check(st, ctx.handle, name)
+            if self.chain_mode:
+                _lib.check(_lib.lib().gf_geom_query_set_chain_mode(q, int(self.chain_mode)), ctx.handle,
+                           "gf_geom_query_set_chain_mode")
+            self._plans.put(key, q)
+        self._last = (ctx, q)
+        return ctx, q
+
+
+class PolygonPolygonRangeQuery(_GeomPairQuery, PolygonPointRangeQuery):
+    """range/PolygonPolygonRangeQuery.java -- a window of polygons against a set of query polygons."""
+
+
+class PolygonLineStringRangeQuery(_GeomPairQuery, PolygonPointRangeQuery):
+    """range/PolygonLineStringRangeQuery.java -- a window of polygons against a set of query linestrings."""
+
+    _query_kind = _lib.GEOM_LINESTRING
+
+
+class LineStringPolygonRangeQuery(_GeomPairQuery, LineStringPointRangeQuery):
+    """range/LineStringPolygonRangeQuery.java -- a window of linestrings against a set of query polygons."""
+
+
+class LineStringLineStringRangeQuery(_GeomPairQuery, LineStringPointRangeQuery):
+    """range/LineStringLineStringRangeQuery.java -- a window of linestrings against a set of query linestrings."""
+
+    _query_kind = _lib.GEOM_LINESTRING
+
+
+class PolygonPolygonKNNQuery(_GeomPairQuery, PolygonPointKNNQuery):
+    """knn/PolygonPolygonKNNQuery.java -- the k polygons of a window nearest to one query polygon within r."""
+
+
+class PolygonLineStringKNNQuery(_GeomPairQuery, PolygonPointKNNQuery):
+    """knn/PolygonLineStringKNNQuery.java -- the k polygons of a window nearest to one query linestring within r."""
+
+    _query_kind = _lib.GEOM_LINESTRING
+
+
+class LineStringPolygonKNNQuery(_GeomPairQuery, LineStringPointKNNQuery):
+    """knn/LineStringPolygonKNNQuery.java -- the k linestrings of a window nearest to one query polygon within r."""
+
+
+class LineStringLineStringKNNQuery(_GeomPairQuery, LineStringPointKNNQuery):
+    """knn/LineStringLineStringKNNQuery.java -- the k linestrings of a window nearest to one query linestring
+    within r."""
+
+    _query_kind = _lib.GEOM_LINESTRING
+
+
 __all__ = [
+    "PolygonPolygonRangeQuery", "PolygonLineStringRangeQuery", "LineStringPolygonRangeQuery", "LineStringLineStringRangeQuery",
+    "PolygonPolygonKNNQuery", "PolygonLineStringKNNQuery", "LineStringPolygonKNNQuery", "LineStringLineStringKNNQuery",
     "GeometryIndex", "PolygonPointRangeQuery", "LineStringPointRangeQuery", "PolygonPointKNNQuery", "LineStringPointKNNQuery",
     "LineString", "LineStringSet", "PointLineStringRangeQuery", "PointLineStringKNNQuery", "PointLineStringJoinQuery",
     "PointPointTJoinQuery", "TJoinResult",
