@@ -1140,7 +1140,7 @@ int  gf_geom_info(const gf_geom_query* q, int64_t* filtered, int64_t* all_guaran
  *     array, offsets not starting at 0, a polygon without a ring, a ring of fewer than 4 vertices or
  *     unclosed, or a chain of fewer than 2 vertices: GF_ERR_ARG from create.  The refusal of rule 2.
  *     Invalid WINDOW objects: rule 6 of the block above.
- * Not covered: RealTime mode, the geometry-stream joins, sliding panes, sharding, JNI.
+ * Not covered: RealTime mode, sliding panes, sharding, JNI.  (The geometry-stream joins: the next block.)
  *
  * gf_geom_query_create_polygons / _linestrings (once per continuous query): the N / G tables of the
  * rectangles, the query CSR, per ring its envelope and the envelopes of its runs of 32 segments (as the
@@ -1154,6 +1154,86 @@ int  gf_geom_query_create_polygons(gf_ctx* ctx, const gf_grid* g, const gf_polyg
 int  gf_geom_query_create_linestrings(gf_ctx* ctx, const gf_grid* g, const gf_linestrings* lines, double r,
                                       int approximate, int metric, gf_geom_query** out);
 int  gf_geom_query_set_chain_mode(gf_geom_query* q, int mode);
+
+/* ---- geometry-stream joins: polygon and linestring windows joined with a second stream -----------
+ * join/PolygonPointJoinQuery.java, LineStringPointJoinQuery.java, PolygonPolygonJoinQuery.java,
+ * PolygonLineStringJoinQuery.java, LineStringPolygonJoinQuery.java, LineStringLineStringJoinQuery.java with
+ * JoinQuery.java:73-137, HelperClass.java:325-376 and UniformGrid.java:165-293, 368-445.  The contract
+ * (derived from the reference and JTS 1.16.1, nothing was run on a JVM):
+ *  1. Sides.  The ORDINARY side is a geometry window (gf_geoms) whose gf_geom_index was prepared on ugrid.
+ *     The QUERY side is a point window (gf_points, with qgrid passed alongside) or a second geometry window
+ *     whose own index was prepared on qgrid.  The two grids may differ, as in the point-point join: cell
+ *     keys are compared as (cx, cy) index pairs, and "valid cell" means valid on qgrid.  Both indexes
+ *     belong to one context.  Rules 1 and 6 of the geometry-window block hold for both sides: the cell
+ *     rectangle R is unclamped, and an invalid object on either side is never paired.
+ *  2. Replication.  Ordinary object o goes to every cell of R_o (ReplicatePolygonStreamUsingObjID /
+ *     ReplicateLineStringStreamUsingObjID), valid or not.  With g the guaranteed and c the candidate layers
+ *     of r on qgrid, query q goes to the cell set K(q):
+ *       a point query: getNeighboringCells(r, q) -- r == 0: every valid cell; r != 0 and c <= 0 (a negative
+ *         or NaN r): GF_ERR_LAYERS; otherwise the valid cells within c layers of the point's cell, which may
+ *         itself lie outside the grid;
+ *       a geometry query: G u C of getReplicated{Polygon,LineString}QueryStream -- the valid cells within c
+ *         layers of some cell of R_q (only when c > 0), and, when g == 0, every cell of R_q with NO validKey,
+ *         so its cells outside the grid are members.  (The g > 0 set lies inside the c set: g < c always.)
+ *         r <= 0 or NaN gives K = {}: no pairs and no error -- rule 2(b) of the block above, not the point rule.
+ *     The union of Chebyshev balls over a rectangle is a rectangle, so the in-grid part of K(q) is
+ *       E_q = [x1 - c, x2 + c] x [y1 - c, y2 + c] n [0, n)^2,
+ *     expanded in 64-bit arithmetic.  Deviation: Java's int sums wrap on saturated indices (a rectangle at
+ *     Integer.MAX_VALUE grows into negative cells); here it grows past the index range and is clipped.
+ *  3. Multiplicity.  Flink's equi-join emits a matching pair once per shared key:
+ *       m(o, q) = |R_o n K(q)| = |R_o n E_q| + [geometry query and g == 0] (|R_o n R_q| - |R_o n R_q n grid|).
+ *     A pair is a candidate iff m > 0.  m is reported per pair as min(m, 2^32 - 1) and computed without
+ *     overflow (a side can be 2^32 cells long); *nrep sums the reported values.
+ *  4. Test.  A candidate is emitted iff d <= r.
+ *     Exact d, point query: getDistance(q, polygon), rule 3 of the geometry-window block, or
+ *       getDistance(q, lineString), the open-chain minimum; either metric.
+ *     Exact d, geometry query: rule 5 of the block above with the operator's own argument order -- the query
+ *       is the FIRST geometry in PolygonPolygon, LineStringLineString and LineStringPolygon; in
+ *       PolygonLineStringJoinQuery the ordinary polygon is first (getDistance(poly, q), lines 161-163).
+ *       segmentToSegment(A, B, C, D) takes AB from the first geometry.
+ *     Approximate d: getPointPolygonBBoxMinEuclideanDistance / getPointLineStringBBoxMinEuclideanDistance on
+ *       the object's envelope for a point query; getBBoxBBoxMinEuclideanDistance(first.boundingBox,
+ *       second.boundingBox) with the same first and second for a geometry query -- the function depends on
+ *       the argument order for degenerate boxes.  Unlike the point-point join, approximate mode still tests
+ *       d <= r.
+ *  5. Result.  An unordered list of distinct (ordinary idx, query idx, m) triples.  RealTime mode calls
+ *     windowBased with slide = size in all six operators: one window evaluation serves both.
+ *  6. Errors, before any device call: a null handle or required pointer, indexes of another context than the
+ *     joiner's, a bad metric, a negative cap, a null `pairs` with cap > 0, first_is_ordinary set for
+ *     anything but a polygon ordinary side and a linestring query side: GF_ERR_ARG.  GF_ERR_LAYERS: rule 2.
+ *     An empty window on either side: no pairs, GF_OK.
+ * Not covered: run envelopes for the first geometry (a long first geometry is walked plainly behind the
+ * box test), a wave form that strides the first geometry, balancing a lane that lands in a dense tile,
+ * sliding panes, sharding, JNI.
+ *
+ * gf_geom_join_create / _destroy: the joiner owns the grow-only scratch of a run (the object and query lists,
+ * the tile CSR, the candidate list) and is reused across windows; like an index it lives on the context
+ * stream.
+ * gf_geom_join_run / _run_points (sync, like gf_join_ppoly_run): pairs = device uint32[3 * cap], (o, q, m) per
+ * pair, at most cap of them written; *npairs = the exact number of distinct pairs, *nrep = the sum of their
+ * m; GF_ERR_CAPACITY iff *npairs > cap (pairs may be null with cap 0, to count).  first_is_ordinary: rule
+ * 4's PolygonLineString order.  Tiles of T x T cells bin the short queries (E_q over at most long_tiles
+ * tiles, no member of K outside the grid) into a CSR; one lane per short object walks the tiles of R_o and
+ * takes a pair only at the tile holding the lower corner of R_o n E_q; long objects and long queries go
+ * through a rectangle pass over pairs.  Exact mode then tests each candidate whose boxes are not provably
+ * farther apart than r by one lane, or by one wave when the SECOND geometry (a point query: the object) has
+ * at least its index's wide_vertices vertices.
+ * gf_geom_join_info (of the last run): pairs with m > 0; exact mode: those dropped by the box test, those
+ * whose distance was evaluated, and those of them by a wave (approximate mode decides in the probe: all
+ * three are 0); objects and queries classed long.
+ * gf_geom_join_set_tuning (tests, tools): tile_side (rounded up to a power of two; 0 = the smallest power of
+ * two >= min(2c + 1, n); either is doubled until the grid has at most 1024 tiles a side), long_tiles (0 =
+ * the default, 16), brute = 1: every pair through the rectangle pass.  Results never depend on it. */
+typedef struct gf_geom_join gf_geom_join;
+int  gf_geom_join_create(gf_ctx* ctx, gf_geom_join** out);
+void gf_geom_join_destroy(gf_geom_join* j);
+int  gf_geom_join_run(gf_geom_join* j, gf_geom_index* ix_ord, gf_geom_index* ix_qry, double r, int approximate, int metric,
+                      int first_is_ordinary, uint32_t* pairs, int64_t cap, int64_t* npairs, int64_t* nrep);
+int  gf_geom_join_run_points(gf_geom_join* j, gf_geom_index* ix_ord, const gf_grid* qgrid, const gf_points* q, double r,
+                             int approximate, int metric, uint32_t* pairs, int64_t cap, int64_t* npairs, int64_t* nrep);
+int  gf_geom_join_info(const gf_geom_join* j, int64_t* candidates, int64_t* box_dropped, int64_t* tested,
+                       int64_t* wave_path, int64_t* long_objects, int64_t* long_queries);
+int  gf_geom_join_set_tuning(gf_geom_join* j, int32_t tile_side, int64_t long_tiles, int brute);
 
 /* ---- pinned host memory ---------------------------------------------------------------
  * Mapped, portable host memory: kernels write kNN records straight into it (pass it as the

@@ -7,7 +7,8 @@ PointPointRangeQuery, PointPolygonRangeQuery, PointPointKNNQuery, PointPointJoin
 PointPolygonKNNQuery, PointPolygonJoinQuery, PointTStatsQuery, PointTAggregateQuery,
 PointPointTKNNQuery, PointPointTJoinQuery, LineString and the PointLineString{Range,KNN,Join}Query
 operators, the PolygonPoint / LineStringPoint {Range,KNN}Query operators over geometry windows, and the
-{Polygon,LineString}{Polygon,LineString}{Range,KNN}Query operators: geometry windows against geometry queries).
+{Polygon,LineString}{Polygon,LineString}{Range,KNN}Query operators: geometry windows against geometry queries;
+{Polygon,LineString}{Point,Polygon,LineString}JoinQuery: geometry windows joined with a second stream).
 """
 from . import _lib, sharding
 from .spatialIndices import UniformGrid, generateCellIDStr, getIntCellIndices, padLeadingZeroesToInt
@@ -24,6 +25,9 @@ from .spatialOperators import (KNNResult, PinnedRecords, PointPointJoinQuery, Po
                                PolygonPolygonRangeQuery, PolygonLineStringRangeQuery, LineStringPolygonRangeQuery,
                                LineStringLineStringRangeQuery, PolygonPolygonKNNQuery, PolygonLineStringKNNQuery,
                                LineStringPolygonKNNQuery, LineStringLineStringKNNQuery,
+                               PolygonPointJoinQuery, LineStringPointJoinQuery, PolygonPolygonJoinQuery,
+                               PolygonLineStringJoinQuery, LineStringPolygonJoinQuery, LineStringLineStringJoinQuery,
+                               GeomJoinResult,
                                PointLineStringJoinQuery, PointLineStringKNNQuery, PointLineStringRangeQuery,
                                PointPolygonRangeQuery, QueryConfiguration, QueryType, RangeResult, assign_cells,
                                bucket_by_cell, knn_merge_host, synthetic_uniform,
@@ -32,6 +36,8 @@ from .spatialStreams import Deserialization
 from .windows import SlidingKNNQuery, SlidingRangeQuery, SlidingWindows
 
 __all__ = [
+    "PolygonPointJoinQuery", "LineStringPointJoinQuery", "PolygonPolygonJoinQuery", "PolygonLineStringJoinQuery",
+    "LineStringPolygonJoinQuery", "LineStringLineStringJoinQuery", "GeomJoinResult",
     "PolygonPolygonRangeQuery", "PolygonLineStringRangeQuery", "LineStringPolygonRangeQuery", "LineStringLineStringRangeQuery",
     "PolygonPolygonKNNQuery", "PolygonLineStringKNNQuery", "LineStringPolygonKNNQuery", "LineStringLineStringKNNQuery",
     "GeometryWindow", "PolygonWindow", "LineStringWindow", "GeometryIndex", "PolygonPointRangeQuery",

@@ -87,6 +87,8 @@ EXPORTS = [
     "gf_geom_index_set_thresholds", "gf_geom_query_create", "gf_geom_query_destroy", "gf_geom_range_run",
     "gf_geom_knn_enqueue", "gf_geom_info",
     "gf_geom_query_create_polygons", "gf_geom_query_create_linestrings", "gf_geom_query_set_chain_mode",
+    "gf_geom_join_create", "gf_geom_join_destroy", "gf_geom_join_run", "gf_geom_join_run_points", "gf_geom_join_info",
+    "gf_geom_join_set_tuning",
 ]
 
 
@@ -327,6 +329,13 @@ def lib():
             "gf_geom_query_create_linestrings": ([P, C.POINTER(GfGrid), C.POINTER(GfLineStrings), d, C.c_int, C.c_int,
                                                  C.POINTER(P)], C.c_int),
             "gf_geom_query_set_chain_mode": ([P, C.c_int], C.c_int),
+            "gf_geom_join_create": ([P, C.POINTER(P)], C.c_int),
+            "gf_geom_join_destroy": ([P], None),
+            "gf_geom_join_run": ([P, P, P, d, C.c_int, C.c_int, C.c_int, P, i64, pi64, pi64], C.c_int),
+            "gf_geom_join_run_points": ([P, P, C.POINTER(GfGrid), C.POINTER(GfPoints), d, C.c_int, C.c_int, P, i64, pi64,
+                                         pi64], C.c_int),
+            "gf_geom_join_info": ([P, pi64, pi64, pi64, pi64, pi64, pi64], C.c_int),
+            "gf_geom_join_set_tuning": ([P, i32, i64, C.c_int], C.c_int),
         }
         for name, (argt, rest) in sig.items():
             if os.environ.get("GF_LIB_PATH") and not hasattr(L, name):

@@ -14,8 +14,7 @@
 #include <cstring>
 
 #include "gf_chain_plan.hpp"
-#include "gf_geom_plan.hpp"
-#include "gf_group.hpp"
+#include "gf_geom_index.hpp"  // struct gf_geom_index: geomjoin.cpp reads it too
 
 using namespace gf;
 
@@ -23,19 +22,6 @@ namespace {
 constexpr size_t kIndexCounters = 4;  // GeomArgs::ictr
 constexpr size_t kQueryCounters = 8;  // GeomArgs::qctr (5 used)
 }  // namespace
-
-struct gf_geom_index {
-  gf_ctx* ctx = nullptr;
-  gf_grid grid{};
-  gf_geoms geoms{};  // the window's device arrays (borrowed)
-  int64_t nrings = 0;
-  int32_t wide_vertices = kGeomWideVertices;
-  DevArr<double> ring_env, env;
-  DevArr<uint8_t> ring_ok, valid;
-  DevArr<uint32_t> ring_wide, work_short, work_wide;
-  DevArr<int32_t> cells, nvert;
-  DevArr<unsigned long long> ctr;
-};
 
 struct gf_geom_query {
   gf_ctx* ctx = nullptr;

@@ -991,6 +991,79 @@ enum GeomPairStage {
   kGeomPairWide = 2,      // one wave per wide object
 };
 hipError_t launch_geompair(gf_ctx* ctx, int stage, const GeomPairArgs& a);
+
+// the geometry-stream joins (k_geomjoin.hip, geomjoin.cpp): two prepared geometry windows, or one and a
+// point window.  A side is what its gf_geom_index holds; the point side (kind 0) has cells only, computed
+// by the bin stage.
+struct GeomJoinSide {
+  int32_t kind;               // GF_GEOM_POLYGON / GF_GEOM_LINESTRING; 0: points
+  int32_t wide_vertices;
+  int64_t n;
+  const int32_t* ring_off;    // null for linestrings
+  const int32_t* vert_off;
+  const double* vx;
+  const double* vy;
+  const double* ring_env;     // minx, maxx, miny, maxy
+  const double* env;          // [n * 4] x1, y1, x2, y2
+  const int32_t* cells;       // [n * 4] cx1, cy1, cx2, cy2
+  const uint8_t* valid;       // null: every entry is valid
+  const int32_t* nvert;
+};
+struct GeomJoinArgs {
+  GeomJoinSide o, q;          // ordinary side, query side
+  const double* px;           // point query
+  const double* py;
+  int32_t* pcells;            // point query: q.cells, written by kGeomJoinPointCells
+  double qminX, qminY, qcl;   // qgrid
+  int32_t n;                  // qgrid partitions: the valid cells are [0, n)^2 whatever grid R_o was taken on
+  int32_t c;                  // candidate layers of r on qgrid
+  int32_t out_members;        // geometry query at guaranteed layers 0: every cell of R_q is in K(q)
+  int32_t whole;              // point query at r == 0: K(q) = every valid cell
+  double r;
+  int approx, metric, first_is_ordinary;
+  int32_t shift;              // tiles of 2^shift cells a side
+  int64_t nt;                 // tiles a side
+  int64_t long_tiles;
+  int brute;
+  uint32_t* short_o;          // [o.n] the lists the class stage appends (per-wave appends: any order)
+  uint32_t* long_o;
+  uint32_t* short_q;          // [q.n]
+  uint32_t* long_q;
+  uint32_t* act_q;            // short and long together
+  uint32_t* tile_cnt;         // [nt^2] (tile, short query) entries per tile
+  uint32_t* tile_off;         // [nt^2 + 1] their exclusive scan
+  uint32_t* tile_cur;         // [nt^2] scatter cursors
+  uint32_t* tile_q;           // [entries] the CSR's query column
+  uint32_t* cand;             // exact mode: (o, q, m) triples, the lane list then the wave list
+  unsigned long long n_lane, n_wave;  // their lengths, from the count pass
+  unsigned long long rect_pairs;      // pairs of the rectangle pass, from the class stage's counters (sizes its launch)
+  uint32_t* pairs;            // the caller's (o, q, m) triples
+  int64_t cap;
+  unsigned long long* ctr;    // kGeomJoinCtr*
+};
+enum GeomJoinCtr {
+  kGeomJoinCtrShortO = 0, kGeomJoinCtrLongO = 1, kGeomJoinCtrShortQ = 2, kGeomJoinCtrLongQ = 3, kGeomJoinCtrActQ = 4,
+  kGeomJoinCtrEntries = 5,     // CSR entries
+  kGeomJoinCtrCand = 6,        // pairs with m > 0
+  kGeomJoinCtrFar = 7,         // exact: candidates dropped by box_far
+  kGeomJoinCtrLane = 8,        // exact: candidates for the lane pass / the wave pass (count pass)
+  kGeomJoinCtrWave = 9,
+  kGeomJoinCtrLaneCur = 10,    // their write cursors
+  kGeomJoinCtrWaveCur = 11,
+  kGeomJoinCtrHits = 12,       // emitted pairs
+  kGeomJoinCtrRep = 13,        // sum of their m
+  kGeomJoinCtrOut = 14,        // write cursor into pairs
+  kGeomJoinCtrs = 16,
+};
+enum GeomJoinStage {
+  kGeomJoinPointCells = 0,  // bin: the cells of the query points
+  kGeomJoinClass = 1,       // bin: objects and queries classed and listed, entries counted per tile
+  kGeomJoinScatter = 2,     // bin: the CSR's query column
+  kGeomJoinProbeCount = 3,  // probe + rectangle pass, counting
+  kGeomJoinProbeWrite = 4,  // probe + rectangle pass, writing candidates (exact) or pairs (approximate)
+  kGeomJoinExact = 5,       // the lane pass and the wave pass
+};
+hipError_t launch_geomjoin(gf_ctx* ctx, int stage, const GeomJoinArgs& a);
 // The record (status 0) of the candidates (cd, co, ci)[0, *count) through the sorted path, any k: two
 // stable radix sorts, (objID, d, idx) -> the first of each objID -> (d, objID, idx) (knn.cpp; the
 // k > kMaxK path of gf_knn_enqueue).  m >= the candidate count sizes the passes; *count and *maybe are

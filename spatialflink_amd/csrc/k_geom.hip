@@ -192,49 +192,7 @@ __global__ __launch_bounds__(kBlock) void geom_exact_short_kernel(GeomArgs a) {
   }
 }
 
-// polygon_distance by one whole wave (every lane calls it with the same arguments; the same value in
-// every lane)
-static __device__ __forceinline__ double polygon_distance_wave(double px, double py, const PolyView& a, int p, int lane) {
-  const int r0 = a.ring_off[p], r1 = a.ring_off[p + 1];
-  if (px == px) {  // NaN x: containment skipped, as polygon_distance
-    const int v0 = a.vert_off[r0], nv = a.vert_off[r0 + 1] - v0;
-    const int loc = locate_in_ring_wave(px, py, a.vx + v0, a.vy + v0, nv, a.ring_env + 4 * r0, lane);
-    if (loc == kLocBoundary) return 0.0;
-    if (loc == kLocInterior) {
-      bool inside = true;
-      for (int h = r0 + 1; h < r1; ++h) {
-        const int hv0 = a.vert_off[h], hnv = a.vert_off[h + 1] - hv0;
-        const int hl = locate_in_ring_wave(px, py, a.vx + hv0, a.vy + hv0, hnv, a.ring_env + 4 * h, lane);
-        if (hl == kLocInterior) { inside = false; break; }
-        if (hl == kLocBoundary) return 0.0;
-      }
-      if (inside) return 0.0;
-    }
-  }
-  double md = 1.7976931348623157e308;
-  for (int rg = r0; rg < r1; ++rg) {
-    const int v0 = a.vert_off[rg], nv = a.vert_off[rg + 1] - v0;
-    if (env_point_distance(a.ring_env + 4 * rg, px, py) > md) continue;  // md is the wave's: the serial skip
-    double l = md;
-    for (int i = lane; i < nv - 1; i += 64) {
-      const double d = point_to_segment(px, py, a.vx[v0 + i], a.vy[v0 + i], a.vx[v0 + i + 1], a.vy[v0 + i + 1], a.metric);
-      if (d < l) l = d;
-    }
-    md = wave_min(l);
-    if (md <= 0.0) return md;
-  }
-  return md;
-}
-static __device__ __forceinline__ double chain_distance_wave(double px, double py, const ChainView& a, int l, int lane) {
-  const int v0 = a.vert_off[l], nseg = a.vert_off[l + 1] - v0 - 1;
-  double md = 1.7976931348623157e308;
-  for (int i = lane; i < nseg; i += 64) {
-    const double d = point_to_segment(px, py, a.vx[v0 + i], a.vy[v0 + i], a.vx[v0 + i + 1], a.vy[v0 + i + 1], a.metric);
-    if (d < md) md = d;
-  }
-  return wave_min(md);
-}
-
+// (polygon_distance_wave / chain_distance_wave: gf_geom_win.hpp, shared with k_geomjoin.hip)
 __global__ __launch_bounds__(kBlock) void geom_exact_wide_kernel(GeomArgs a) {
   const int lane = threadIdx.x & 63;
   const int64_t cnt = (int64_t)a.qctr[1];  // <= nobj

@@ -12,6 +12,8 @@ evaluates that window on the GPU through the C ABI -- the body of apply() is wha
   PointLineStringRangeQuery.run(window, Set<LineString>, r) -- range/PointLineStringRangeQuery.java:100-172
   PointLineStringKNNQuery.run(window, LineString, r, k)     -- knn/PointLineStringKNNQuery.java (windowBased)
   PointLineStringJoinQuery.run(points, lineStrings, r)      -- join/PointLineStringJoinQuery.java (windowBased)
+  {Polygon,LineString}{Point,Polygon,LineString}JoinQuery.run(ordinary, query, r)
+                                                      -- join/*JoinQuery.java (windowBased): geometry windows joined
 
 Errors follow the reference: unsupported query types raise ValueError ("Not yet support",
 IllegalArgumentException), candidate layers <= 0 raise CandidateLayersError (System.exit(1)).
@@ -1776,7 +1778,169 @@ class LineStringLineStringKNNQuery(_GeomPairQuery, LineStringPointKNNQuery):
     _query_kind = _lib.GEOM_LINESTRING
 
 
+# ----------------------------------------------------------------------------------------
+# geometry-stream joins: a polygon / linestring window joined with a second stream
+# ----------------------------------------------------------------------------------------
+@dataclass
+class GeomJoinResult:
+    """The distinct pairs of one join window, sorted by (ordinary index, query index), each with its
+    multiplicity m = the number of cell keys the pair shares (min(m, 2^32 - 1)): Flink's equi-join emits
+    the pair once per shared key."""
+    pairs: np.ndarray         # int64 [n, 2]
+    multiplicity: np.ndarray  # int64 [n]
+    nrep: int                 # the sum of the multiplicities, as the device counted it
+
+    def replicated(self) -> np.ndarray:
+        """the reference's output multiset: every pair repeated m times, int64 [nrep, 2]"""
+        return np.repeat(self.pairs, self.multiplicity, axis=0)
+
+
+class _GeomJoinQuery(SpatialOperator):
+    """What the six geometry-stream joins share (gf_geom_join_run / gf_geom_join_run_points): the ordinary
+    window's index on uGrid, the query side on qGrid, one joiner per device reused across windows.
+    RealTime calls windowBased with slide = size in the reference, so both query types run the same window
+    evaluation.  tile_side / long_tiles / brute are gf_geom_join_set_tuning's (tests, tools); results never
+    depend on them."""
+
+    _kind = _lib.GEOM_POLYGON
+    _query_kind = 0          # 0: a point window
+    _first_is_ordinary = 0   # PolygonLineStringJoinQuery: getDistance(polygon, lineString)
+    tile_side = 0
+    long_tiles = 0
+    brute = 0
+
+    def __init__(self, conf: QueryConfiguration, uGrid: UniformGrid, qGrid: UniformGrid = None):
+        super().__init__(conf, uGrid)
+        self.index2 = qGrid if qGrid is not None else uGrid
+        self._joiners = {}
+        self._last = None
+
+    def _joiner(self, ctx):
+        j = self._joiners.get(ctx.device)
+        if j is None:
+            j = C.c_void_p()
+            _lib.check(_lib.lib().gf_geom_join_create(ctx.handle, C.byref(j)), ctx.handle, "gf_geom_join_create")
+            self._joiners[ctx.device] = j
+        return j
+
+    @staticmethod
+    def _side(name, window, index, kind, grid):
+        """(index, made here) of a geometry side, checked as _GeomWindowQuery._index checks its window"""
+        if not isinstance(window, GeometryWindow) or window.kind != kind:
+            raise ValueError(f"{name}: the window holds the other kind of geometry")
+        if index is None:
+            return GeometryIndex(window, grid), True
+        if index.window is not window:
+            raise ValueError("the index was prepared for another window")
+        return index, False
+
+    def run(self, ordinaryWindow, queryWindow, queryRadius: float, index: GeometryIndex = None,
+            query_index: GeometryIndex = None) -> GeomJoinResult:
+        import torch
+
+        _require_supported(self.conf)
+        name = type(self).__name__
+        if self._query_kind == 0 and not isinstance(queryWindow, PointWindow):
+            raise ValueError(f"{name}: the query window must be a PointWindow")
+        ix, own = self._side(name, ordinaryWindow, index, self._kind, self.index)
+        qix, qown = (None, False) if self._query_kind == 0 else self._side(name, queryWindow, query_index, self._query_kind,
+                                                                           self.index2)
+        dev = ordinaryWindow.vert_off.device
+        ctx = _lib.context(dev.index)
+        L = _lib.lib()
+        j = self._joiner(ctx)
+        _lib.check(L.gf_geom_join_set_tuning(j, int(self.tile_side), int(self.long_tiles), int(self.brute)), ctx.handle,
+                   "gf_geom_join_set_tuning")
+        self._last = (ctx, j)
+        approx, metric = int(self.conf.approximateQuery), int(self.conf.distanceMetric)
+        pts = queryWindow.c_struct() if qix is None else None
+        cap = max(1024, 2 * (ordinaryWindow.n + queryWindow.n))
+        try:
+            for _ in range(2):
+                pairs = torch.empty(3 * cap, dtype=torch.int32, device=dev)
+                npairs, nrep = C.c_int64(), C.c_int64()
+                if qix is None:
+                    what = "gf_geom_join_run_points"
+                    st = L.gf_geom_join_run_points(j, ix.handle, C.byref(self.index2.c_grid), C.byref(pts), float(queryRadius),
+                                                   approx, metric, pairs.data_ptr(), cap, C.byref(npairs), C.byref(nrep))
+                else:
+                    what = "gf_geom_join_run"
+                    st = L.gf_geom_join_run(j, ix.handle, qix.handle, float(queryRadius), approx, metric,
+                                            int(self._first_is_ordinary), pairs.data_ptr(), cap, C.byref(npairs), C.byref(nrep))
+                if st == _lib.GF_ERR_CAPACITY:
+                    cap = int(npairs.value)
+                    continue
+                _lib.check(st, ctx.handle, what)
+                m = int(npairs.value)
+                out = pairs[: 3 * m].cpu().numpy().view(np.uint32).astype(np.int64).reshape(-1, 3)
+                out = out[np.lexsort((out[:, 1], out[:, 0]))]
+                return GeomJoinResult(np.ascontiguousarray(out[:, :2]), np.ascontiguousarray(out[:, 2]), int(nrep.value))
+            raise _lib.GeoFlinkError(_lib.GF_ERR_CAPACITY, "join output kept growing")
+        finally:
+            if own:
+                ix.close()  # (the run calls are synchronous: nothing in flight reads the index)
+            if qown:
+                qix.close()
+
+    def info(self) -> dict:
+        """gf_geom_join_info of the last run"""
+        ctx, j = self._last
+        v = [C.c_int64() for _ in range(6)]
+        _lib.check(_lib.lib().gf_geom_join_info(j, *(C.byref(c) for c in v)), ctx.handle, "gf_geom_join_info")
+        return dict(zip(("candidates", "box_dropped", "tested", "wave_path", "long_objects", "long_queries"),
+                        (c.value for c in v)))
+
+    def close(self):
+        joiners, self._joiners = getattr(self, "_joiners", {}), {}
+        for j in joiners.values():
+            if _lib._lib is not None:
+                _lib._lib.gf_geom_join_destroy(j)
+
+    def __del__(self):
+        self.close()
+
+
+class PolygonPointJoinQuery(_GeomJoinQuery):
+    """join/PolygonPointJoinQuery.java -- a polygon stream joined with a point stream."""
+
+
+class LineStringPointJoinQuery(_GeomJoinQuery):
+    """join/LineStringPointJoinQuery.java -- a linestring stream joined with a point stream."""
+
+    _kind = _lib.GEOM_LINESTRING
+
+
+class PolygonPolygonJoinQuery(_GeomJoinQuery):
+    """join/PolygonPolygonJoinQuery.java -- a polygon stream joined with a polygon stream."""
+
+    _query_kind = _lib.GEOM_POLYGON
+
+
+class PolygonLineStringJoinQuery(_GeomJoinQuery):
+    """join/PolygonLineStringJoinQuery.java -- a polygon stream joined with a linestring stream; the distance
+    takes the ORDINARY polygon first (getDistance(poly, q)), unlike the other five."""
+
+    _query_kind = _lib.GEOM_LINESTRING
+    _first_is_ordinary = 1
+
+
+class LineStringPolygonJoinQuery(_GeomJoinQuery):
+    """join/LineStringPolygonJoinQuery.java -- a linestring stream joined with a polygon stream."""
+
+    _kind = _lib.GEOM_LINESTRING
+    _query_kind = _lib.GEOM_POLYGON
+
+
+class LineStringLineStringJoinQuery(_GeomJoinQuery):
+    """join/LineStringLineStringJoinQuery.java -- a linestring stream joined with a linestring stream."""
+
+    _kind = _lib.GEOM_LINESTRING
+    _query_kind = _lib.GEOM_LINESTRING
+
+
 __all__ = [
+    "PolygonPointJoinQuery", "LineStringPointJoinQuery", "PolygonPolygonJoinQuery", "PolygonLineStringJoinQuery",
+    "LineStringPolygonJoinQuery", "LineStringLineStringJoinQuery", "GeomJoinResult",
     "PolygonPolygonRangeQuery", "PolygonLineStringRangeQuery", "LineStringPolygonRangeQuery", "LineStringLineStringRangeQuery",
     "PolygonPolygonKNNQuery", "PolygonLineStringKNNQuery", "LineStringPolygonKNNQuery", "LineStringLineStringKNNQuery",
     "GeometryIndex", "PolygonPointRangeQuery", "LineStringPointRangeQuery", "PolygonPointKNNQuery", "LineStringPointKNNQuery",
