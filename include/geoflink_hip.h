@@ -597,6 +597,89 @@ int gf_geojson_parse(gf_ctx* ctx, gf_objid_dict* dict, const char* text, int64_t
                      const gf_grid* grid, double* x, double* y, int64_t* objID, int64_t* ts, int32_t* cx,
                      int32_t* cy, int64_t cap, int64_t* n_out, int64_t* bad_line, int32_t* bad_kind);
 
+/* ---- GeoJSON ingest of polygon and linestring streams -----------------------------------
+ * Deserialization.GeoJSONToSpatialPolygon / GeoJSONToTSpatialPolygon (Deserialization.java:327-458)
+ * and GeoJSONToSpatialLineString / GeoJSONToTSpatialLineString (:623-745) over a chunk of lines:
+ * text in, a geometry window (gf_geoms, below) out, on the device, ready for gf_geom_prepare.
+ *
+ * Shared with gf_geojson_parse (same code): the line is the Kafka record or, with value_lines, its
+ * value V; strict JSON as Jackson reads it; V missing or not an object: GF_CSV_MISSING_FIELD; the
+ * number rule (correctly rounded; an integral literal is (double) of its long, "-0" -> +0.0; a
+ * float overflowing to Infinity or an integer outside long anywhere on the line: unsupported);
+ * "properties" (time property, objID property, date_format, tz_offset_minutes, escapes, objID
+ * keys through the dictionary); CRLF, a missing final newline, empty lines (GF_CSV_EMPTY_LINE),
+ * nesting deeper than 256; the first bad line wins (GF_ERR_ARG, *bad_line, *bad_kind).  The non-T
+ * deserializers are this call with both property names NULL: objID null, ts 0.
+ *
+ * Which geometry is taken (the maps' try / catch, :346-355, :641-650): V's own "type" names a
+ * geometry -> V's "coordinates"; on failure, or for "Feature" / a missing / unknown "type" ->
+ * V."geometry".  FeatureCollection: unsupported.  The taken geometry's "type" must be "Polygon" or
+ * "MultiPolygon" (kind GF_GEOM_POLYGON), "LineString" or "MultiLineString" (GF_GEOM_LINESTRING);
+ * any other GeoJSON geometry type is GF_CSV_UNSUPPORTED (the reference pushes it through the wrong
+ * bracket depth).
+ *
+ * What JTS must accept (GeoJsonReader builds the geometry first; the kinds are this library's
+ * labels, the reference only throws):
+ *  - every position is an array whose ordinates 0 and 1 are numbers, else GF_CSV_NUMBER_FORMAT;
+ *  - a non-array where a position, ring or polygon array is expected: GF_CSV_MISSING_FIELD;
+ *  - every ring of a Polygon, and of every polygon of a MultiPolygon, has at least 4 positions and
+ *    first == last (Coordinate.equals2D: x == x and y == y of the parsed doubles, so -0.0 closes
+ *    0.0), else GF_CSV_MISSING_FIELD;
+ *  - every linestring, every member of a MultiLineString included, has at least 2 positions, else
+ *    GF_CSV_MISSING_FIELD.
+ * Within one geometry the first failure in document order is the line's; ring closure is tested
+ * after the structure of the whole geometry.
+ *
+ * The coordinates the object gets.  The reference re-reads V.toString() with a string splitter
+ * (convertCoordinates / convertMultiCoordinates / splitString / findCountN, :1382-1427, :1531-1592)
+ * that starts at the text's first '[', counts bracket depth and splits on "],".  On Jackson's
+ * compact re-serialisation that equals the plain structural reading of the taken "coordinates"
+ * exactly under these conditions; everything else is GF_CSV_UNSUPPORTED, never guessed:
+ *  - no '[' or ']' byte in V's text before the '[' of the taken "coordinates" (a bbox, an
+ *    array-valued property, a bracket inside a string); nor a backslash there (an escape can spell
+ *    a bracket that the re-serialisation writes out).  Anything after the array is free;
+ *  - every position has exactly two ordinates (a third stops the splitter from closing rings);
+ *  - no empty array at any level of the taken "coordinates";
+ *  - no duplicate member name in V or in the taken geometry object (Jackson keeps the first
+ *    position and the last value);
+ *  - if V's own geometry fails and the catch branch's "geometry" succeeds, the splitter still
+ *    reads V's first bracket: unsupported.
+ *
+ * The window object (what the operators read: .polygon, .lineString):
+ *  - Polygon: its rings in createPolygon order (Polygon.java:147-165): one ring as is; several by
+ *    descending area with the insertion rule of createPolygonArray (:115-145: appended while the
+ *    last ring's area >= its own -- equal areas keep input order --, else inserted before the
+ *    first ring whose area <= its own), the largest the shell.  The area is the plain shoelace
+ *    sum x1*y2 - x2*y1 in ring order, fp64, no contraction, abs / 2 -- the one spatialObjects.Polygon
+ *    uses, so the window is bit-identical to that host mirror's.  JTS's own getArea is believed to
+ *    use an x-shifted form (not verifiable without JTS): rings whose order differs between the two
+ *    forms, and rings whose area is not a number, are outside the contract.  Closing and padding
+ *    never trigger: JTS has required closed rings of at least 4 positions.
+ *  - MultiPolygon: its FIRST polygon only (MultiPolygon.java:32-45); the later ones are validated
+ *    and dropped.  LineString: its positions.  MultiLineString: its FIRST linestring
+ *    (MultiLineString.java:30-50).
+ *  - objID and ts from "properties" as for points.
+ *
+ * The call is synchronous; text is device bytes, 16-byte aligned, shorter than 8 GiB.  On success
+ * *nobj / *nrings / *nverts are exact and the arrays form a valid gf_geoms: offsets start at 0 and
+ * are monotone, ring_off[nobj] == nrings, vert_off[last] == nverts (linestrings: *nrings = 0).
+ * If any capacity is too small: GF_ERR_CAPACITY with all three exact counts and nothing promised
+ * about the arrays; all capacities 0 with NULL arrays is the legal way to ask for the sizes.
+ * Totals that do not fit int32 offsets: GF_ERR_ARG.  Argument errors are reported before any
+ * device call.  Not restated here: WKT and CSV/TSV geometry lines, MultiPoint and
+ * GeometryCollection streams. */
+typedef struct {            /* device arrays the parse fills; capacities in elements */
+  int32_t kind;             /* GF_GEOM_POLYGON | GF_GEOM_LINESTRING: which stream constructor */
+  int64_t obj_cap, ring_cap, vert_cap;
+  int32_t* ring_off;        /* [obj_cap + 1]; polygons only (NULL for linestrings) */
+  int32_t* vert_off;        /* polygons [ring_cap + 1]; linestrings [obj_cap + 1] */
+  double *vx, *vy;          /* [vert_cap] */
+  int64_t *objID, *ts;      /* [obj_cap] */
+} gf_geoms_out;
+int gf_geojson_parse_geoms(gf_ctx* ctx, gf_objid_dict* dict /* NULL: the context's */, const char* text, int64_t len,
+                           const gf_geojson_schema* schema, const gf_geoms_out* out, int64_t* nobj, int64_t* nrings,
+                           int64_t* nverts, int64_t* bad_line, int32_t* bad_kind);
+
 /* ---- join (sync) --------------------------------------------------------------------
  * JoinQuery.getReplicatedPointQueryStream + PointPointJoinQuery.windowBased
  * (JoinQuery.java:73-90, PointPointJoinQuery.java:124-183).  pairs: device uint32[2*cap]

@@ -339,11 +339,13 @@ struct GeoPos {
   int64_t V, tV, cV, gV, tG, cG, prV, tsP, qP;
   bool escV, escG, escP;
 };
-enum { kTyNone, kTyPoint, kTyOtherGeom, kTyFeature, kTyFeatureColl, kTyEscaped };
+enum { kTyNone, kTyPoint, kTyOtherGeom, kTyFeature, kTyFeatureColl, kTyEscaped,
+       // geo_type_full only (the geometry streams, gf_geojson_geom.hpp): kTyOtherGeom told apart
+       kTyLineString, kTyPolygon, kTyMultiPoint, kTyMultiLineString, kTyMultiPolygon, kTyGeomColl };
 // a "type" member's value: JTS's geometry types ("Point" restated, the rest not), GeoJSON's
 // Feature / FeatureCollection, anything else (absent, not a String, unknown) -> kTyNone
 template <class Src>
-GF_DHD inline int geo_type(const Src& s, int64_t t, int64_t e) {
+GF_DHD inline int geo_type_full(const Src& s, int64_t t, int64_t e) {
   if (t < 0 || s(t) != '"') return kTyNone;
   bool esc = false;
   const int64_t te = jstr_end(s, t, e, &esc);
@@ -356,12 +358,20 @@ GF_DHD inline int geo_type(const Src& s, int64_t t, int64_t e) {
     return true;
   };
   if (is("Point", 5)) return kTyPoint;
-  if (is("LineString", 10) || is("Polygon", 7) || is("MultiPoint", 10) || is("MultiLineString", 15) ||
-      is("MultiPolygon", 12) || is("GeometryCollection", 18))
-    return kTyOtherGeom;
+  if (is("LineString", 10)) return kTyLineString;
+  if (is("Polygon", 7)) return kTyPolygon;
+  if (is("MultiPoint", 10)) return kTyMultiPoint;
+  if (is("MultiLineString", 15)) return kTyMultiLineString;
+  if (is("MultiPolygon", 12)) return kTyMultiPolygon;
+  if (is("GeometryCollection", 18)) return kTyGeomColl;
   if (is("Feature", 7)) return kTyFeature;
   if (is("FeatureCollection", 17)) return kTyFeatureColl;
   return kTyNone;
+}
+template <class Src>
+GF_DHD inline int geo_type(const Src& s, int64_t t, int64_t e) {
+  const int ty = geo_type_full(s, t, e);
+  return ty >= kTyLineString ? (int)kTyOtherGeom : ty;
 }
 // GeoJsonReader.createPoint: coordinates = a list whose ordinates 0, 1 (and 2, if present) are
 // Numbers (ordinates.get(i).doubleValue(); anything else throws ClassCastException ->
@@ -500,10 +510,10 @@ GF_DHD GF_NOINLINE int geo_eval(const GeoProps& a, const Src& s, int64_t e, cons
 
 // The slow path: Jackson's strict parse, then member-by-member lookup (jfind) -- exact on any
 // line (escapes, deep nesting, malformed ones).  p: the line's first non-blank byte, a '{'.
+// the walk's member-by-member lookup over a line that passed jvalidate: kCsvOk and *gp, or
+// kCsvUnsupported (the record has a member name written with an escape)
 template <class Src>
-GF_DHD GF_NOINLINE int eval_geojson_walk(GeoProps a, Src s, int64_t p, int64_t e, int vlines, LineOut* o) {
-  const int vs = jvalidate(s, p, e, a.pow5);
-  if (vs) return vs;
+GF_DHD inline int geo_walk_find(const GeoProps& a, const Src& s, int64_t p, int64_t e, int vlines, GeoPos* gp) {
   GeoPos g{-1, -1, -1, -1, -1, -1, -1, -1, -1, false, false, false};
   // member `k` of the object at obj (when it is one); false: obj has an escaped member name
   auto find = [&](int64_t obj, const char* k, int kl, int64_t* out) {
@@ -522,6 +532,16 @@ GF_DHD GF_NOINLINE int eval_geojson_walk(GeoProps a, Src s, int64_t p, int64_t e
   find(g.gV, "coordinates", 11, &g.cG);
   g.escP = !find(g.prV, a.kts, a.len_ts >= 0 ? a.len_ts : 0, &g.tsP);
   find(g.prV, a.kobj, a.len_obj >= 0 ? a.len_obj : 0, &g.qP);
+  *gp = g;
+  return kCsvOk;
+}
+template <class Src>
+GF_DHD GF_NOINLINE int eval_geojson_walk(GeoProps a, Src s, int64_t p, int64_t e, int vlines, LineOut* o) {
+  const int vs = jvalidate(s, p, e, a.pow5);
+  if (vs) return vs;
+  GeoPos g;
+  const int fs = geo_walk_find(a, s, p, e, vlines, &g);
+  if (fs) return fs;
   return geo_eval(a, s, e, g, o);
 }
 

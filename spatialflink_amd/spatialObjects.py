@@ -383,10 +383,19 @@ class GeometryWindow:
     nobj: int
     start: int = 0
     end: int = 0
+    objid_dict: Optional[ObjIdDict] = None   # the dictionary of its non-numeric objID keys (ingest)
 
     @property
     def n(self) -> int:
         return int(self.nobj)
+
+    def objid_strings(self, keys=None):
+        """Strings of objID keys (default: every object's), as PointWindow.objid_strings."""
+        import torch
+
+        k = self.objID.cpu().numpy() if keys is None else np.asarray(keys, np.int64)
+        dev = self.objID.device.index if self.objID.is_cuda else torch.cuda.current_device()
+        return (self.objid_dict or ObjIdDict.default(dev)).decode(k)
 
     @classmethod
     def from_csr(cls, kind, ring_off, vert_off, vx, vy, objID=None, ts=None, device=None, start=0, end=0):

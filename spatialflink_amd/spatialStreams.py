@@ -11,6 +11,10 @@ objID keys (the objID field is a String, :317 -- canonical decimals are their va
 String goes through the device dictionary, k_objid.hip), ts and the cells (cx, cy) -- no
 per-point host work.  A bad line raises ValueError naming
 it (the reference's map throws NumberFormatException / IndexOutOfBoundsException).
+
+The polygon and linestring streams (GeoJSONTo[T]SpatialPolygon, :327-458; GeoJSONTo[T]SpatialLineString,
+:623-745) go through gf_geojson_parse_geoms (k_geomingest.hip): lines of GeoJSON in, a
+PolygonWindow / LineStringWindow (device CSR, ready for the geometry-window operators) out.
 """
 from __future__ import annotations
 
@@ -19,7 +23,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .spatialObjects import ObjIdDict, PointWindow
+from .spatialObjects import LineStringWindow, ObjIdDict, PointWindow, PolygonWindow
 
 
 class GfCsvSchema(C.Structure):
@@ -87,7 +91,91 @@ def _parse_lines(fn, schema, uGrid, text, device, capacity, objid_dict):
     return w
 
 
+def _parse_geoms(kind, schema, text, device, objid_dict):
+    """gf_geojson_parse_geoms: one sizing call (zero capacities), then the exact-size call."""
+    import torch
+
+    t = device_text(text, device)
+    dev = t.device
+    ctx = _lib.context(dev.index)
+    d = objid_dict or ObjIdDict.default(dev.index)
+    poly = kind == _lib.GEOM_POLYGON
+    nobj, nr, nv, bl, bk = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int32()
+    ptr = lambda a: a.data_ptr() if a is not None else None  # noqa: E731
+
+    def call(out):
+        st = _lib.lib().gf_geojson_parse_geoms(ctx.handle, d.handle, C.c_void_p(t.data_ptr()), int(t.numel()),
+                                               C.byref(schema), C.byref(out), C.byref(nobj), C.byref(nr), C.byref(nv),
+                                               C.byref(bl), C.byref(bk))
+        if st == _lib.GF_ERR_ARG and bl.value >= 0:
+            raise ValueError(f"line {bl.value}: {CSV_KINDS.get(bk.value, bk.value)}")
+        return st
+
+    st = call(_lib.GfGeomsOut(kind, 0, 0, 0, None, None, None, None, None, None))  # the sizes
+    if st != _lib.GF_ERR_CAPACITY:
+        _lib.check(st, ctx.handle, "gf_geojson_parse_geoms")
+    n, r, v = nobj.value, nr.value, nv.value
+    ro = torch.zeros(n + 1, dtype=torch.int32, device=dev) if poly else None
+    vo = torch.zeros((r if poly else n) + 1, dtype=torch.int32, device=dev)
+    vx = torch.empty(v, dtype=torch.float64, device=dev)
+    vy = torch.empty(v, dtype=torch.float64, device=dev)
+    o = torch.empty(n, dtype=torch.int64, device=dev)
+    ts = torch.empty(n, dtype=torch.int64, device=dev)
+    if n > 0:  # (empty text: the zeroed offsets are the empty window)
+        _lib.check(call(_lib.GfGeomsOut(kind, n, r, v, ptr(ro), ptr(vo), ptr(vx), ptr(vy), ptr(o), ptr(ts))),
+                   ctx.handle, "gf_geojson_parse_geoms")
+    cls = PolygonWindow if poly else LineStringWindow
+    return cls(int(kind), ro, vo, vx, vy, o, ts, nobj.value, objid_dict=d)
+
+
+class _GeoJSONToGeoms:
+    """The four geometry-stream deserializers: lines of GeoJSON -> a geometry window on the GPU
+    (gf_geojson_parse_geoms; the contract is in include/geoflink_hip.h).  The lines, the number
+    rule and the properties are GeoJSONToTSpatial's; the object is the taken Polygon's rings in
+    createPolygon order / the LineString's positions, a Multi*'s first member only."""
+
+    kind = None
+
+    def __init__(self, uGrid=None, dateFormat=None, propertyTimeStamp=None, propertyObjID=None, tz_offset_minutes=0,
+                 value_lines=False):
+        if dateFormat not in GEOJSON_DATE_FORMATS:
+            raise ValueError(f"dateFormat {dateFormat!r}: supported {list(GEOJSON_DATE_FORMATS)}")
+        self.uGrid = uGrid
+        self._names = (propertyObjID.encode() if propertyObjID else None,
+                       propertyTimeStamp.encode() if propertyTimeStamp else None)
+        self.schema = GfGeojsonSchema(self._names[0], self._names[1], GEOJSON_DATE_FORMATS[dateFormat],
+                                      int(tz_offset_minutes), int(bool(value_lines)))
+
+    def parse(self, text, device=None, objid_dict: ObjIdDict = None):
+        return _parse_geoms(self.kind, self.schema, text, device, objid_dict)
+
+
+class _GeoJSONToGeomsPlain(_GeoJSONToGeoms):
+    """The non-T deserializers: no properties are read (objID null, ts 0)."""
+
+    def __init__(self, uGrid=None, value_lines=False):
+        super().__init__(uGrid, None, None, None, 0, value_lines)
+
+
 class Deserialization:
+    class GeoJSONToTSpatialPolygon(_GeoJSONToGeoms):
+        """GeoJSONToTSpatialPolygon(uGrid, dateFormat, propertyTimeStamp, propertyObjID)
+        (Deserialization.java:389-458) -> PolygonWindow."""
+        kind = _lib.GEOM_POLYGON
+
+    class GeoJSONToSpatialPolygon(_GeoJSONToGeomsPlain):
+        """GeoJSONToSpatialPolygon(uGrid) (Deserialization.java:327-387) -> PolygonWindow."""
+        kind = _lib.GEOM_POLYGON
+
+    class GeoJSONToTSpatialLineString(_GeoJSONToGeoms):
+        """GeoJSONToTSpatialLineString(uGrid, dateFormat, propertyTimeStamp, propertyObjID)
+        (Deserialization.java:683-745) -> LineStringWindow."""
+        kind = _lib.GEOM_LINESTRING
+
+    class GeoJSONToSpatialLineString(_GeoJSONToGeomsPlain):
+        """GeoJSONToSpatialLineString(uGrid) (Deserialization.java:623-681) -> LineStringWindow."""
+        kind = _lib.GEOM_LINESTRING
+
     class GeoJSONToTSpatial:
         """GeoJSONToTSpatial(uGrid, dateFormat, propertyTimeStamp, propertyObjID)
         (Deserialization.java:149-211) over lines of GeoJSON, run on the GPU (gf_geojson_parse):
