@@ -8,10 +8,10 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off -fno-f
 SRC      := spatialflink_amd/csrc
 OBJDIR   := build/obj
 LIB      := spatialflink_amd/libgeoflink_hip.so
-SOURCES  := $(SRC)/ctx.cpp $(SRC)/grid.cpp $(SRC)/range.cpp $(SRC)/knn.cpp $(SRC)/join.cpp $(SRC)/window.cpp $(SRC)/comm.cpp $(SRC)/sliding.cpp $(SRC)/csv.cpp $(SRC)/objid.cpp $(SRC)/traj.cpp $(SRC)/tagg.cpp $(SRC)/tknn.cpp $(SRC)/tjoin.cpp $(SRC)/trange.cpp $(SRC)/geom.cpp $(SRC)/geomjoin.cpp $(SRC)/geomingest.cpp $(SRC)/k_points.hip $(SRC)/k_knn.hip \
-            $(SRC)/k_range.hip $(SRC)/k_join.hip $(SRC)/k_csv.hip $(SRC)/k_objid.hip $(SRC)/k_traj.hip $(SRC)/k_tagg.hip $(SRC)/k_tknn.hip $(SRC)/k_tjoin.hip $(SRC)/k_trange.hip $(SRC)/k_geom.hip $(SRC)/k_geompair.hip $(SRC)/k_geomjoin.hip $(SRC)/k_geomingest.hip
+SOURCES  := $(SRC)/ctx.cpp $(SRC)/grid.cpp $(SRC)/range.cpp $(SRC)/knn.cpp $(SRC)/join.cpp $(SRC)/window.cpp $(SRC)/comm.cpp $(SRC)/sliding.cpp $(SRC)/csv.cpp $(SRC)/objid.cpp $(SRC)/traj.cpp $(SRC)/tagg.cpp $(SRC)/tknn.cpp $(SRC)/tjoin.cpp $(SRC)/trange.cpp $(SRC)/geom.cpp $(SRC)/geomjoin.cpp $(SRC)/geomingest.cpp $(SRC)/wktingest.cpp $(SRC)/k_points.hip $(SRC)/k_knn.hip \
+            $(SRC)/k_range.hip $(SRC)/k_join.hip $(SRC)/k_csv.hip $(SRC)/k_objid.hip $(SRC)/k_traj.hip $(SRC)/k_tagg.hip $(SRC)/k_tknn.hip $(SRC)/k_tjoin.hip $(SRC)/k_trange.hip $(SRC)/k_geom.hip $(SRC)/k_geompair.hip $(SRC)/k_geomjoin.hip $(SRC)/k_geomingest.hip $(SRC)/k_wktingest.hip
 OBJECTS  := $(patsubst $(SRC)/%,$(OBJDIR)/%.o,$(SOURCES))
-HEADERS  := include/geoflink_hip.h $(SRC)/gf_buildtag.hpp $(SRC)/gf_units.hpp $(SRC)/gf_internal.hpp $(SRC)/gf_host.hpp $(SRC)/gf_text.hpp $(SRC)/gf_geojson.hpp $(SRC)/gf_numerics.hpp $(SRC)/gf_decimal.hpp $(SRC)/gf_pow5.hpp $(SRC)/gf_geom.hpp $(SRC)/gf_group.hpp $(SRC)/gf_trange_plan.hpp $(SRC)/gf_chain_plan.hpp $(SRC)/gf_geom_plan.hpp $(SRC)/gf_geom_win.hpp $(SRC)/gf_geom_index.hpp $(SRC)/gf_geomjoin_plan.hpp $(SRC)/gf_geojson_geom.hpp $(SRC)/k_geomingest.hpp
+HEADERS  := include/geoflink_hip.h $(SRC)/gf_buildtag.hpp $(SRC)/gf_units.hpp $(SRC)/gf_internal.hpp $(SRC)/gf_host.hpp $(SRC)/gf_text.hpp $(SRC)/gf_geojson.hpp $(SRC)/gf_numerics.hpp $(SRC)/gf_decimal.hpp $(SRC)/gf_pow5.hpp $(SRC)/gf_geom.hpp $(SRC)/gf_group.hpp $(SRC)/gf_trange_plan.hpp $(SRC)/gf_chain_plan.hpp $(SRC)/gf_geom_plan.hpp $(SRC)/gf_geom_win.hpp $(SRC)/gf_geom_index.hpp $(SRC)/gf_geomjoin_plan.hpp $(SRC)/gf_geojson_geom.hpp $(SRC)/k_geomingest.hpp $(SRC)/gf_wkt_geom.hpp $(SRC)/k_wktingest.hpp
 
 all: $(LIB) oracle shim
 

@@ -666,8 +666,8 @@ int gf_geojson_parse(gf_ctx* ctx, gf_objid_dict* dict, const char* text, int64_t
  * If any capacity is too small: GF_ERR_CAPACITY with all three exact counts and nothing promised
  * about the arrays; all capacities 0 with NULL arrays is the legal way to ask for the sizes.
  * Totals that do not fit int32 offsets: GF_ERR_ARG.  Argument errors are reported before any
- * device call.  Not restated here: WKT and CSV/TSV geometry lines, MultiPoint and
- * GeometryCollection streams. */
+ * device call.  Not restated here: CSV/TSV geometry lines, MultiPoint and GeometryCollection
+ * streams (WKT lines: gf_wkt_parse_geoms, below). */
 typedef struct {            /* device arrays the parse fills; capacities in elements */
   int32_t kind;             /* GF_GEOM_POLYGON | GF_GEOM_LINESTRING: which stream constructor */
   int64_t obj_cap, ring_cap, vert_cap;
@@ -679,6 +679,85 @@ typedef struct {            /* device arrays the parse fills; capacities in elem
 int gf_geojson_parse_geoms(gf_ctx* ctx, gf_objid_dict* dict /* NULL: the context's */, const char* text, int64_t len,
                            const gf_geojson_schema* schema, const gf_geoms_out* out, int64_t* nobj, int64_t* nrings,
                            int64_t* nverts, int64_t* bad_line, int32_t* bad_kind);
+
+/* ---- WKT ingest of point, polygon and linestring streams -----------------------------------
+ * Deserialization.WKTToSpatial / WKTToTSpatial (Deserialization.java:214-232, :261-288),
+ * WKTToSpatialPolygon / WKTToTSpatialPolygon (:461-490, :524-586) and WKTToSpatialLineString /
+ * WKTToTSpatialLineString (:748-835) with their WKTReader helpers (:1456-1528), over a chunk of
+ * lines on the device.  Per line:
+ *
+ * Which text is read.  The geometry text starts at the first byte-exact, case-sensitive occurrence
+ * of the tag, as String.indexOf finds it: polygons "MULTIPOLYGON" if it occurs, else "POLYGON";
+ * linestrings "MULTILINESTRING" if it occurs, else "LINESTRING"; points "POINT".  No occurrence
+ * (a lower-case tag included): the reference's substring(-1) throws, GF_CSV_MISSING_FIELD.  The
+ * occurrence is taken where it is found -- inside a longer word, inside the line's first field --
+ * and the grammar below decides.  Everything after the geometry's closing ')' is free (a T line's
+ * time field, a closing quote, the "} of a Kafka record).
+ *
+ * The canonical grammar; every other text is GF_CSV_UNSUPPORTED or a failure where any WKT reader
+ * must fail, never guessed: the tag, optional blanks (space or tab), '('; parentheses nested to the
+ * depth the tag implies; members separated by ',' with optional blanks around them; a position is
+ * exactly two number tokens separated by blanks; a number token is a maximal run of the bytes
+ * 0-9 + - . e E and its value is Double.parseDouble of the token, correctly rounded.
+ *  - GF_CSV_UNSUPPORTED: anything but blanks between the tag and its '(' (Z, M, ZM, EMPTY, a tag
+ *    run-on such as POLYGONZ); EMPTY anywhere; a third number in a position; a token holding any
+ *    other letter (NaN, Infinity, a d / f suffix, hexadecimal); '#', a byte >= 0x80 or a control
+ *    byte other than tab inside the geometry text; a literal of more than 19 significant digits
+ *    within 1e-19 of a rounding boundary (as GF_CSV_UNSUPPORTED of gf_csv_parse); a line of 2 GiB;
+ *  - GF_CSV_NUMBER_FORMAT: a token of the allowed bytes that parseDouble rejects (1.2.3, -, e5);
+ *  - GF_CSV_MISSING_FIELD (this library's label; the reference only throws): a position with one
+ *    number, a line that ends before the geometry closes, a wrong bracket, an empty member list.
+ *
+ * What JTS must accept: every ring of the polygon (of every polygon of a MULTIPOLYGON) has at least
+ * 4 positions and is closed under Coordinate.equals2D on the parsed doubles; every linestring, every
+ * MULTILINESTRING member included, has at least 2 positions; else GF_CSV_MISSING_FIELD.  The first
+ * failure in document order is the line's; ring closure is tested after the structure of the whole
+ * geometry.
+ *
+ * The window object.  Polygon: exterior then interiors as getPolygonCoordinates lists them, then the
+ * createPolygon order -- the same code and the same shoelace area as gf_geojson_parse_geoms.
+ * MULTIPOLYGON: its first polygon only (the later ones are validated and dropped).  LINESTRING: its
+ * positions.  MULTILINESTRING: its first member.  POINT: x and y of the one position, with cx, cy
+ * when a grid is given.
+ *
+ * objID and ts (the T variants: delimiter != 0).  The line with every '"' removed is split by
+ * gf_csv_parse's "\\s*delimiter\\s*" rule.  objID = field 0 after Java trim(), or null when the
+ * trimmed field starts with one of the stream's two tags; it becomes a key as in gf_csv_parse_dict
+ * (a canonical decimal is its value, any other String goes through the dictionary).  ts:
+ * date_format 0 -> 0; date_format 1 -> the fields from the last to the first, each trimmed, through
+ * gf_geojson_parse's date parser (SimpleDateFormat.parse reads a prefix), the first that parses; none
+ * -> 0; a date before 1583 in a tried field: GF_CSV_UNSUPPORTED.  The reference's quirk (:577-582) is
+ * kept: a POLYGON whose ts is 0 (a date that parses to the epoch included) is built by
+ * Polygon(list, uGrid), so its objID is null; a MULTIPOLYGON and both linestring kinds keep their
+ * objID at ts 0.  The fields are read before the geometry, as the maps do.  The non-T maps
+ * (delimiter 0) read no field: objID null, ts 0.
+ *
+ * gf_wkt_parse_geoms follows every convention of gf_geojson_parse_geoms (gf_geoms_out and its kind;
+ * device text, 16-byte aligned, shorter than 8 GiB; CRLF, a missing final newline; an empty line is
+ * GF_CSV_EMPTY_LINE; all-zero capacities with NULL arrays is the sizing call; GF_ERR_CAPACITY returns
+ * the three exact counts; the first bad line wins with GF_ERR_ARG, *bad_line, *bad_kind; argument
+ * errors before any device call; totals past int32 offsets are GF_ERR_ARG; len == 0 is a valid empty
+ * window).  gf_wkt_parse_points follows gf_csv_parse (outputs, capacity rule, bad-line report); both
+ * point maps build Point(x, y, uGrid) -- the T variant ignores its date format and delimiter -- so
+ * objID is GF_OBJID_NULL and ts 0 on every line, and the call takes no schema.
+ * Rests on JTS 1.16.1 (not verifiable without it): WKTReader.read stops after the first
+ * geometry; the tokenizer's character classes; the LinearRing / LineString size and closure checks;
+ * no normalisation; getCoordinates in text order. */
+typedef struct {
+  char delimiter;            /* T variants: one character, as gf_csv_schema.delimiter: any byte is taken as
+                                is and matched literally (not as a regex), except '"', which is GF_ERR_ARG:
+                                every '"' is removed before the split, so it could never split;
+                                0: the non-T deserializers (objID null, ts 0, no field is read) */
+  char reserved[3];
+  int32_t date_format;       /* 0: dateFormat == null (ts 0); 1: "yyyy-MM-dd HH:mm:ss" */
+  int32_t tz_offset_minutes; /* as gf_geojson_schema */
+} gf_wkt_schema;
+int gf_wkt_parse_geoms(gf_ctx* ctx, gf_objid_dict* dict /* NULL: the context's */, const char* text, int64_t len,
+                       const gf_wkt_schema* schema, const gf_geoms_out* out, int64_t* nobj, int64_t* nrings,
+                       int64_t* nverts, int64_t* bad_line, int32_t* bad_kind);
+int gf_wkt_parse_points(gf_ctx* ctx, const char* text, int64_t len, const gf_grid* grid, double* x, double* y,
+                        int64_t* objID, int64_t* ts, int32_t* cx, int32_t* cy, int64_t cap, int64_t* n_out,
+                        int64_t* bad_line, int32_t* bad_kind);
 
 /* ---- join (sync) --------------------------------------------------------------------
  * JoinQuery.getReplicatedPointQueryStream + PointPointJoinQuery.windowBased

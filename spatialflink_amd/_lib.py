@@ -62,7 +62,7 @@ EXPORTS = [
     "gf_knn_sliding_create", "gf_knn_sliding_destroy", "gf_knn_sliding_geometry", "gf_knn_sliding_push",
     "gf_knn_sliding_flush", "gf_knn_sliding_decode", "gf_range_sliding_create", "gf_range_sliding_destroy",
     "gf_range_sliding_geometry", "gf_range_sliding_push", "gf_pane_bounds", "gf_csv_parse", "gf_csv_parse_dict", "gf_geojson_parse",
-    "gf_geojson_parse_geoms",
+    "gf_geojson_parse_geoms", "gf_wkt_parse_geoms", "gf_wkt_parse_points",
     "gf_objid_dict_create", "gf_objid_dict_destroy", "gf_ctx_objid_dict", "gf_objid_dict_size", "gf_objid_intern",
     "gf_objid_decode", "gf_join_pp", "gf_join_pp_async",
     "gf_join_ppoly_plan_create", "gf_join_ppoly_run", "gf_join_ppoly",
@@ -233,6 +233,8 @@ def lib():
             "gf_geojson_parse": ([P, P, P, i64, P, C.POINTER(GfGrid), P, P, P, P, P, P, i64, pi64, pi64, pi32],
                                  C.c_int),
             "gf_geojson_parse_geoms": ([P, P, P, i64, P, C.POINTER(GfGeomsOut), pi64, pi64, pi64, pi64, pi32], C.c_int),
+            "gf_wkt_parse_geoms": ([P, P, P, i64, P, C.POINTER(GfGeomsOut), pi64, pi64, pi64, pi64, pi32], C.c_int),
+            "gf_wkt_parse_points": ([P, P, i64, C.POINTER(GfGrid), P, P, P, P, P, P, i64, pi64, pi64, pi32], C.c_int),
             "gf_csv_parse_dict": ([P, P, P, i64, P, C.POINTER(GfGrid), P, P, P, P, P, P, i64, pi64, pi64, pi32],
                                   C.c_int),
             "gf_objid_dict_create": ([P, C.POINTER(P)], C.c_int),

@@ -314,6 +314,22 @@ struct RingTmp {
   int32_t* count;
   int32_t* order;  // createPolygonArray's list: ring indices by descending area
 };
+// t.order = createPolygonArray's list over t.area[0 .. nrings) (shared with the WKT ingest, gf_wkt_geom.hpp)
+GF_DHD inline void ring_order(const RingTmp& t, int32_t nrings) {
+  int32_t m = 0;
+  for (int32_t r = 0; r < nrings; ++r) {
+    const double ar = t.area[r];
+    if (m == 0 || t.area[t.order[m - 1]] >= ar) {
+      t.order[m++] = r;
+      continue;
+    }
+    int32_t at = 0;
+    while (at < m && !(t.area[t.order[at]] <= ar)) ++at;  // (found: the last one is smaller; m: an area is NaN)
+    for (int32_t k = m; k > at; --k) t.order[k] = t.order[k - 1];
+    t.order[at] = r;
+    ++m;
+  }
+}
 // The taken object of a good line (closure checked) -> vx / vy at vbase; a polygon's rings in
 // createPolygon order (Polygon.java:147-165; several rings: createPolygonArray's insertion rule,
 // :115-145 -- a ring is appended while the last area >= its own, else inserted before the first
@@ -340,19 +356,7 @@ GF_DHD inline void geom_fill(const Src& s, int64_t e, const GeomNote& n, const u
     t.area[r] = (a2 < 0.0 ? -a2 : a2) / 2.0;
     i = jarr_next(s, end, e);
   }
-  int32_t m = 0;
-  for (int32_t r = 0; r < n.nrings; ++r) {
-    const double ar = t.area[r];
-    if (m == 0 || t.area[t.order[m - 1]] >= ar) {
-      t.order[m++] = r;
-      continue;
-    }
-    int32_t at = 0;
-    while (at < m && !(t.area[t.order[at]] <= ar)) ++at;  // (found: the last one is smaller; m: an area is NaN)
-    for (int32_t k = m; k > at; --k) t.order[k] = t.order[k - 1];
-    t.order[at] = r;
-    ++m;
-  }
+  ring_order(t, n.nrings);
   int32_t off = vbase;
   for (int32_t k = 0; k < n.nrings; ++k) {
     const int32_t r = t.order[k];

@@ -42,6 +42,7 @@ struct gf_ctx {
   unsigned long long* geojson_check = nullptr;  // GF_FLAG_GEOJSON_CHECK: the 4 counters (device; null: off)
   int64_t csv_mean_line[2] = {0, 0};  // per format (CSV, GeoJSON): the last call's mean line length (sizes the next one's LDS staging)
   int64_t geom_mean_line = 0;  // gf_geojson_parse_geoms: the last call's mean line length (as csv_mean_line)
+  int64_t wkt_mean_line[2] = {0, 0};  // gf_wkt_parse_geoms, gf_wkt_parse_points: the same
   int join_async_done = 0;  // gf_join_pp_async: the packing kernel wrote the count
   double join_ppp = 0.0;  // pairs per ordinary point of the last join (sizes the output chunks)
   hipStream_t aux = nullptr;   // kNN depth >= 3: the second stream of windows in flight (created on first use)

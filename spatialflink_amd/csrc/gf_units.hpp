@@ -7,6 +7,6 @@
 
 #define GF_UNITS(X)                                                                            \
   X(ctx, cpp) X(grid, cpp) X(range, cpp) X(knn, cpp) X(join, cpp) X(window, cpp) X(comm, cpp)  \
-  X(sliding, cpp) X(csv, cpp) X(objid, cpp) X(traj, cpp) X(tagg, cpp) X(tknn, cpp) X(tjoin, cpp) X(trange, cpp) X(geom, cpp) X(geomjoin, cpp) X(geomingest, cpp) X(k_points, hip) X(k_knn, hip) \
+  X(sliding, cpp) X(csv, cpp) X(objid, cpp) X(traj, cpp) X(tagg, cpp) X(tknn, cpp) X(tjoin, cpp) X(trange, cpp) X(geom, cpp) X(geomjoin, cpp) X(geomingest, cpp) X(wktingest, cpp) X(k_points, hip) X(k_knn, hip) \
   X(k_range, hip) X(k_join, hip) X(k_csv, hip) X(k_objid, hip) X(k_traj, hip) X(k_tagg, hip) \
-  X(k_tknn, hip) X(k_tjoin, hip) X(k_trange, hip) X(k_geom, hip) X(k_geompair, hip) X(k_geomjoin, hip) X(k_geomingest, hip)
+  X(k_tknn, hip) X(k_tjoin, hip) X(k_trange, hip) X(k_geom, hip) X(k_geompair, hip) X(k_geomjoin, hip) X(k_geomingest, hip) X(k_wktingest, hip)

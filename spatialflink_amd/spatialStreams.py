@@ -91,8 +91,9 @@ def _parse_lines(fn, schema, uGrid, text, device, capacity, objid_dict):
     return w
 
 
-def _parse_geoms(kind, schema, text, device, objid_dict):
-    """gf_geojson_parse_geoms: one sizing call (zero capacities), then the exact-size call."""
+def _parse_geoms(kind, schema, text, device, objid_dict, fn="gf_geojson_parse_geoms"):
+    """gf_geojson_parse_geoms / gf_wkt_parse_geoms: one sizing call (zero capacities), then the
+    exact-size call."""
     import torch
 
     t = device_text(text, device)
@@ -104,16 +105,15 @@ def _parse_geoms(kind, schema, text, device, objid_dict):
     ptr = lambda a: a.data_ptr() if a is not None else None  # noqa: E731
 
     def call(out):
-        st = _lib.lib().gf_geojson_parse_geoms(ctx.handle, d.handle, C.c_void_p(t.data_ptr()), int(t.numel()),
-                                               C.byref(schema), C.byref(out), C.byref(nobj), C.byref(nr), C.byref(nv),
-                                               C.byref(bl), C.byref(bk))
+        st = getattr(_lib.lib(), fn)(ctx.handle, d.handle, C.c_void_p(t.data_ptr()), int(t.numel()), C.byref(schema),
+                                     C.byref(out), C.byref(nobj), C.byref(nr), C.byref(nv), C.byref(bl), C.byref(bk))
         if st == _lib.GF_ERR_ARG and bl.value >= 0:
             raise ValueError(f"line {bl.value}: {CSV_KINDS.get(bk.value, bk.value)}")
         return st
 
     st = call(_lib.GfGeomsOut(kind, 0, 0, 0, None, None, None, None, None, None))  # the sizes
     if st != _lib.GF_ERR_CAPACITY:
-        _lib.check(st, ctx.handle, "gf_geojson_parse_geoms")
+        _lib.check(st, ctx.handle, fn)
     n, r, v = nobj.value, nr.value, nv.value
     ro = torch.zeros(n + 1, dtype=torch.int32, device=dev) if poly else None
     vo = torch.zeros((r if poly else n) + 1, dtype=torch.int32, device=dev)
@@ -123,7 +123,7 @@ def _parse_geoms(kind, schema, text, device, objid_dict):
     ts = torch.empty(n, dtype=torch.int64, device=dev)
     if n > 0:  # (empty text: the zeroed offsets are the empty window)
         _lib.check(call(_lib.GfGeomsOut(kind, n, r, v, ptr(ro), ptr(vo), ptr(vx), ptr(vy), ptr(o), ptr(ts))),
-                   ctx.handle, "gf_geojson_parse_geoms")
+                   ctx.handle, fn)
     cls = PolygonWindow if poly else LineStringWindow
     return cls(int(kind), ro, vo, vx, vy, o, ts, nobj.value, objid_dict=d)
 
@@ -157,7 +157,161 @@ class _GeoJSONToGeomsPlain(_GeoJSONToGeoms):
         super().__init__(uGrid, None, None, None, 0, value_lines)
 
 
+class GfWktSchema(C.Structure):
+    _fields_ = [("delimiter", C.c_char), ("reserved", C.c_char * 3), ("date_format", C.c_int32),
+                ("tz_offset_minutes", C.c_int32)]
+
+
+class _WKTToGeoms:
+    """The four WKT geometry-stream deserializers: lines holding a WKT geometry -> a geometry window
+    on the GPU (gf_wkt_parse_geoms; the contract is in include/geoflink_hip.h).  The T variants
+    split the line by `delimiter` for the objID (field 0) and the time (the last field that parses
+    as `dateFormat`)."""
+
+    kind = None
+
+    def __init__(self, uGrid=None, dateFormat=None, delimiter=",", tz_offset_minutes=0):
+        if dateFormat not in GEOJSON_DATE_FORMATS:
+            raise ValueError(f"dateFormat {dateFormat!r}: supported {list(GEOJSON_DATE_FORMATS)}")
+        if len(delimiter) != 1 or delimiter in "\0\"":
+            raise ValueError("single-character delimiters only (not '\"': it is removed before the split)")
+        self.uGrid = uGrid
+        self.schema = GfWktSchema(delimiter.encode(), b"\0\0\0", GEOJSON_DATE_FORMATS[dateFormat],
+                                  int(tz_offset_minutes))
+
+    def parse(self, text, device=None, objid_dict: ObjIdDict = None):
+        return _parse_geoms(self.kind, self.schema, text, device, objid_dict, "gf_wkt_parse_geoms")
+
+
+class _WKTToGeomsPlain(_WKTToGeoms):
+    """The non-T deserializers: no field is read (objID null, ts 0)."""
+
+    def __init__(self, uGrid=None):
+        self.uGrid = uGrid
+        self.schema = GfWktSchema(b"\0", b"\0\0\0", 0, 0)
+
+
+class _WKTToPoints:
+    """WKTToSpatial / WKTToTSpatial: both maps build Point(x, y, uGrid) from the line's POINT, so
+    objID is null and ts 0 on every line (gf_wkt_parse_points)."""
+
+    def __init__(self, uGrid=None):
+        self.uGrid = uGrid
+
+    def parse(self, text, device=None, objid_dict: ObjIdDict = None) -> PointWindow:
+        import torch
+
+        t = device_text(text, device)
+        dev = t.device
+        ctx = _lib.context(dev.index)
+        d = objid_dict or ObjIdDict.default(dev.index)
+        n = int(t.numel())
+        g = self.uGrid
+        cap = max(1, n // 16 + 1)
+        nout, bl, bk = C.c_int64(), C.c_int64(), C.c_int32()
+        while True:
+            x = torch.empty(cap, dtype=torch.float64, device=dev)
+            y = torch.empty(cap, dtype=torch.float64, device=dev)
+            o = torch.empty(cap, dtype=torch.int64, device=dev)
+            ts = torch.empty(cap, dtype=torch.int64, device=dev)
+            cx = torch.empty(cap, dtype=torch.int32, device=dev) if g is not None else None
+            cy = torch.empty(cap, dtype=torch.int32, device=dev) if g is not None else None
+            st = _lib.lib().gf_wkt_parse_points(
+                ctx.handle, C.c_void_p(t.data_ptr()), n, C.byref(g.c_grid) if g is not None else None, x.data_ptr(),
+                y.data_ptr(), o.data_ptr(), ts.data_ptr(), cx.data_ptr() if g is not None else None,
+                cy.data_ptr() if g is not None else None, cap, C.byref(nout), C.byref(bl), C.byref(bk))
+            if st == _lib.GF_ERR_CAPACITY:
+                cap = nout.value
+                continue
+            if st == _lib.GF_ERR_ARG and bl.value >= 0:
+                raise ValueError(f"line {bl.value}: {CSV_KINDS.get(bk.value, bk.value)}")
+            _lib.check(st, ctx.handle, "gf_wkt_parse_points")
+            break
+        m = nout.value
+        w = PointWindow(x[:m], y[:m], o[:m], ts[:m], objid_dict=d)
+        if g is not None:
+            w.extra["cx"], w.extra["cy"] = cx[:m], cy[:m]
+        return w
+
+
 class Deserialization:
+    class WKTToSpatial(_WKTToPoints):
+        """WKTToSpatial(uGrid) (Deserialization.java:214-232) -> PointWindow."""
+
+    class WKTToTSpatial(_WKTToPoints):
+        """WKTToTSpatial(uGrid, dateFormat, delimiter) (Deserialization.java:261-288) -> PointWindow; the
+        reference's map reads neither its date format nor its delimiter."""
+
+        def __init__(self, uGrid=None, dateFormat=None, delimiter=","):
+            super().__init__(uGrid)
+
+    class WKTToSpatialPolygon(_WKTToGeomsPlain):
+        """WKTToSpatialPolygon(uGrid) (Deserialization.java:461-490) -> PolygonWindow."""
+        kind = _lib.GEOM_POLYGON
+
+    class WKTToTSpatialPolygon(_WKTToGeoms):
+        """WKTToTSpatialPolygon(uGrid, dateFormat, delimiter) (Deserialization.java:524-586) -> PolygonWindow."""
+        kind = _lib.GEOM_POLYGON
+
+    class WKTToSpatialLineString(_WKTToGeomsPlain):
+        """WKTToSpatialLineString(uGrid) (Deserialization.java:748-776) -> LineStringWindow."""
+        kind = _lib.GEOM_LINESTRING
+
+    class WKTToTSpatialLineString(_WKTToGeoms):
+        """WKTToTSpatialLineString(uGrid, dateFormat, delimiter) (Deserialization.java:778-835) ->
+        LineStringWindow."""
+        kind = _lib.GEOM_LINESTRING
+
+    # ---- the reference's dispatchers (Deserialization.java:47-115, :588-621): the map for an inputType ----
+    @staticmethod
+    def PointStream(inputType, delimiter=",", csvTsvSchemaAttr=(0, 1, 2, 3), uGrid=None):
+        if inputType == "WKT":
+            return Deserialization.WKTToSpatial(uGrid)
+        raise ValueError("Not yet support")  # GeoJSONToSpatial / CSVTSVToSpatial: the non-T point maps
+
+    @staticmethod
+    def TrajectoryStream(inputType, dateFormat=None, delimiter=",", csvTsvSchemaAttr=(0, 1, 2, 3),
+                         propertyTimeStamp=None, propertyObjID=None, uGrid=None):
+        if inputType == "GeoJSON":
+            return Deserialization.GeoJSONToTSpatial(uGrid, dateFormat, propertyTimeStamp, propertyObjID)
+        if inputType == "WKT":
+            return Deserialization.WKTToTSpatial(uGrid, dateFormat, delimiter)
+        return Deserialization.CSVTSVToTSpatial(uGrid, dateFormat, delimiter, csvTsvSchemaAttr)
+
+    @staticmethod
+    def PolygonStream(inputType, uGrid=None):
+        if inputType == "GeoJSON":
+            return Deserialization.GeoJSONToSpatialPolygon(uGrid)
+        if inputType == "WKT":
+            return Deserialization.WKTToSpatialPolygon(uGrid)
+        raise ValueError(f"inputType : {inputType} is not support")
+
+    @staticmethod
+    def TrajectoryStreamPolygon(inputType, dateFormat=None, delimiter=",", propertyTimeStamp=None, propertyObjID=None,
+                                uGrid=None):
+        if inputType == "GeoJSON":
+            return Deserialization.GeoJSONToTSpatialPolygon(uGrid, dateFormat, propertyTimeStamp, propertyObjID)
+        if inputType == "WKT":
+            return Deserialization.WKTToTSpatialPolygon(uGrid, dateFormat, delimiter)
+        raise ValueError(f"inputType : {inputType} is not support")
+
+    @staticmethod
+    def LineStringStream(inputType, uGrid=None):
+        if inputType == "GeoJSON":
+            return Deserialization.GeoJSONToSpatialLineString(uGrid)
+        if inputType == "WKT":
+            return Deserialization.WKTToSpatialLineString(uGrid)
+        raise ValueError(f"inputType : {inputType} is not support")
+
+    @staticmethod
+    def TrajectoryStreamLineString(inputType, dateFormat=None, delimiter=",", propertyTimeStamp=None,
+                                   propertyObjID=None, uGrid=None):
+        if inputType == "GeoJSON":
+            return Deserialization.GeoJSONToTSpatialLineString(uGrid, dateFormat, propertyTimeStamp, propertyObjID)
+        if inputType == "WKT":
+            return Deserialization.WKTToTSpatialLineString(uGrid, dateFormat, delimiter)
+        raise ValueError(f"inputType : {inputType} is not support")
+
     class GeoJSONToTSpatialPolygon(_GeoJSONToGeoms):
         """GeoJSONToTSpatialPolygon(uGrid, dateFormat, propertyTimeStamp, propertyObjID)
         (Deserialization.java:389-458) -> PolygonWindow."""
